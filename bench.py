@@ -20,10 +20,24 @@ value = all ranks' pixels / max-over-ranks time.  Ranks must sit on distinct GPU
 
 Prints ONE JSON line on rank 0.  `roofline` is the embed kernel (the dominant one):
 algorithmic bytes per launch / its mean launch time from HIP events on the launch
-stream.  `cpu_baseline` times the oracle (oracle/, a C port of the reference's
-arithmetic) on a bounded sample on this host's cores; the same sample's oracle outputs
-are compared with the timed batch's GPU outputs (`parity_sample`), and a mismatch
-makes the run fail.
+stream.
+
+A plain run does only what `value` needs: set up, warm up, time `--steps` steps, write
+the outputs (`--dump-outputs DIR`) and print the line; the fields of the legs below are
+null in it.  `--full` adds every other leg, after the timed region unless noted:
+`embed_work_sample` (one untimed embed call before the timed steps that counts the
+blocks of each pass), `exact_route_check` (the timed output against the GPU's reference
+route), `cpu_baseline` (the oracle -- oracle/, a C port of the reference's arithmetic --
+on a bounded sample on this host's cores; the same sample's oracle outputs are compared
+with the timed batch's GPU outputs, `parity_sample` / `lapack_route_sample`),
+`cpu_baseline_reference_model` and the measured copy rate
+(`roofline.torch_copy_measured_GBs`).  A mismatch in any comparison makes the run fail.
+
+`--dump-outputs DIR` writes what the last timed step computed -- the watermarked frames
+(`embed_out.npy`) and the extracted tiles (`extract_tiles.npy`), float32 -- whole when
+small, else a fixed seeded sample of every frame (dump_outputs).  The inputs are
+synthetic with fixed seeds, so two builds run with the same arguments can be compared
+output for output.
 """
 from __future__ import annotations
 
@@ -53,6 +67,14 @@ def parse(argv=None):
     p.add_argument("--width", type=int, default=3840)
     p.add_argument("--block", type=int, default=8)
     p.add_argument("--alpha", type=float, default=0.1)
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beside the headline figure: the embed work sample, the reference-route "
+                        "check of the timed output, the CPU baselines with their parity samples and the measured "
+                        "copy rate (the options below size them; without --full none of them runs)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's outputs to DIR/embed_out.npy and "
+                        "DIR/extract_tiles.npy (float32; a fixed seeded sample of every frame when large; "
+                        "N > 1: <name>.rank<r>.npy per rank)")
     p.add_argument("--cpu-frames", type=int, default=48,
                    help="frames in the CPU-baseline / parity sample, ~10-20 s of oracle work on 16 cores (0 = skip)")
     p.add_argument("--no-cpu-baseline", action="store_true")
@@ -331,6 +353,38 @@ def lib_build_id():
         return None
 
 
+DUMP_SEED = 0x5EED0D0
+DUMP_ELEMS = {"embed_out": 1 << 23, "extract_tiles": 1 << 22}  # float32: 32 MiB + 16 MiB
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """Write each (n, ...) uint8 tensor of `arrays` as path/<name>.npy in float32 (N > 1:
+    <name>.rank<r>.npy).  An array of at most DUMP_ELEMS[name] elements is written whole, in
+    its own shape; a larger one as (n, k): k elements of every frame at positions drawn once
+    per frame from a generator seeded with DUMP_SEED, the same in every run of the same shape."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        cap = DUMP_ELEMS[name]
+        n = t.shape[0]
+        flat = t.reshape(n, -1)
+        per = flat.shape[1] if n else 0
+        if n * per <= cap:
+            a = t.cpu().numpy().astype(np.float32)
+        else:
+            n = min(n, cap)
+            k = max(1, cap // n)
+            pos = torch.from_numpy(np.random.default_rng(DUMP_SEED).integers(0, per, size=(n, k), dtype=np.int64))
+            c = max(1, ((1 << 31) - 1) // per)  # frames per gather: 32-bit indexable chunks
+            a = np.empty((n, k), dtype=np.float32)
+            for s in range(0, n, c):
+                e = min(n, s + c)
+                a[s:e] = torch.gather(flat[s:e], 1, pos[s:e].to(flat.device)).cpu().numpy()
+        np.save(os.path.join(path, name + (f".rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
 def run(args, kernels=None, device=None):
     """One rank of the benchmark.  `kernels` / `device` default to the HIP path on this
     rank's GPU; the CPU test of the multi-rank code substitutes its own (tests/)."""
@@ -340,6 +394,9 @@ def run(args, kernels=None, device=None):
 
     from thatsmyface_amd.dist import ShardedRoundTrip, max_over_ranks, shard_range
 
+    full = getattr(args, "full", False)
+    if not full:  # a plain run: none of the legs beside the headline figure
+        args = argparse.Namespace(**dict(vars(args), cpu_frames=0, lapack_frames=0, structured_crops=0, exact_frames=0))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -402,12 +459,12 @@ def run(args, kernels=None, device=None):
     rt.hooks.append(hook)
     for _ in range(args.warmup):
         rt.step()
-    # how one embed call over this rank's whole batch splits its work (untimed; the same bytes
+    # --full: how one embed call over this rank's whole batch splits its work (untimed; the same bytes
     # are rewritten, and every embed launch of the run has the same size, so a kernel trace's
     # averages are the timed launches'): blocks the strip pass left to the list pass, blocks
     # on the dgesdd route
     work = None
-    if hasattr(K, "embed_stats") and stop > start:
+    if full and hasattr(K, "embed_stats") and stop > start:
         st = K.embed_stats(frames, wm, b, alpha, rt.out)
         work = {"frames": stop - start, "blocks": (stop - start) * nbh * nbw,
                 "list_pass_blocks": st.get("list_pass_blocks"), "dgesdd_route_blocks": st.get("lapack_blocks")}
@@ -424,6 +481,8 @@ def run(args, kernels=None, device=None):
         dist.barrier()
     sync()
     elapsed = max_over_ranks(time.perf_counter() - t0, dev)
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, {"embed_out": rt.out, "extract_tiles": rt.tiles}, rank, world)
     ev = list(zip(marks["broadcast"], marks["embed"], marks["extract"]))
     if on_gpu:
         embed_ms = sum(a.elapsed_time(m) for a, m, _ in ev) / len(ev)
@@ -563,7 +622,7 @@ def run(args, kernels=None, device=None):
             "per_crop_s": round(sum(r[0] for r in res) / k, 2),
             "crops_bit_exact_vs_gpu": f"{same}/{k}",
         }
-    copy_gbs = measured_copy_peak(torch, dev) if rank == 0 and on_gpu else None
+    copy_gbs = measured_copy_peak(torch, dev) if full and rank == 0 and on_gpu else None
     build = lib_build_id() if on_gpu else None
 
     # Counter-derived figures (tools/pmc_embed.sh -> tools/valu.py -> profiles/valu.json) are

@@ -51,7 +51,7 @@ def test_workload_names():
 
 def test_bench_two_ranks_gloo(tmp_path, capfd):
     F, H, W, B, A = 3, 48, 80, 8, 0.1
-    argv = ["--gpus", "2", "--backend", "gloo", "--frames", str(F), "--height", str(H), "--width", str(W),
+    argv = ["--gpus", "2", "--backend", "gloo", "--full", "--frames", str(F), "--height", str(H), "--width", str(W),
             "--steps", "1", "--warmup", "0", "--block", str(B), "--alpha", str(A)]
     os.environ["TMF_BENCH_DUMP"] = str(tmp_path)
     try:
@@ -99,7 +99,7 @@ def test_bench_eight_ranks_gloo(tmp_path):
     the union of the 8 shards equals a serial oracle run, every rank holds rank 0's tile,
     and every rank's parity share (frames spread over its shard) is reported."""
     F, H, W, B, A = 2, 32, 48, 8, 0.1
-    argv = ["--gpus", "8", "--backend", "gloo", "--frames", str(F), "--height", str(H), "--width", str(W),
+    argv = ["--gpus", "8", "--backend", "gloo", "--full", "--frames", str(F), "--height", str(H), "--width", str(W),
             "--steps", "1", "--warmup", "1", "--block", str(B), "--alpha", str(A), "--cpu-frames", "16",
             "--lapack-frames", "8"]
     r = _spawn(argv, tmp_path)
@@ -139,7 +139,7 @@ def test_bench_eight_ranks_failure_ends_run(tmp_path, mode):
     """A rank that raises, fails parity or hangs makes the 8-rank run end with a non-zero
     status, with no rank left waiting in a collective (the hang ends through --pg-timeout)."""
     F, H, W = 1, 16, 32
-    argv = ["--gpus", "8", "--backend", "gloo", "--frames", str(F), "--height", str(H), "--width", str(W),
+    argv = ["--gpus", "8", "--backend", "gloo", "--full", "--frames", str(F), "--height", str(H), "--width", str(W),
             "--steps", "1", "--warmup", "1", "--cpu-frames", "8", "--lapack-frames", "0", "--pg-timeout", "20"]
     import time
 
@@ -161,7 +161,7 @@ def test_bench_one_rank_cpu_baselines(tmp_path, capfd):
     F, H, W, B = 2, 48, 80, 8
     env = dict(os.environ, TMF_BENCH_DUMP=str(tmp_path))
     env.pop("WORLD_SIZE", None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_rank_cpu.py"), "--frames", str(F), "--height",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_rank_cpu.py"), "--full", "--frames", str(F), "--height",
                           str(H), "--width", str(W), "--steps", "1", "--warmup", "0", "--cpu-frames", "2",
                           "--structured-crops", "2"], env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -177,3 +177,58 @@ def test_bench_one_rank_cpu_baselines(tmp_path, capfd):
 
     if _CORE == "SkylakeX":
         assert rm["crops_bit_exact_vs_gpu"] == "2/2"
+
+
+def _plain(tmp_path, extra, F=3, H=48, W=80):
+    env = dict(os.environ, TMF_BENCH_DUMP=str(tmp_path))
+    env.pop("WORLD_SIZE", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_rank_cpu.py"), "--frames", str(F), "--height",
+                        str(H), "--width", str(W), "--steps", "2", "--warmup", "1"] + extra,
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the run times its steps and nothing else: the legs beside the headline figure
+    report null, the headline fields stay.  --dump-outputs writes the last timed step's outputs
+    (small arrays whole, float32), equal to the oracle's on the same seeded inputs, and the same
+    bytes from run to run."""
+    F, H, W, B, A = 3, 48, 80, 8, 0.1
+    d1, d2 = tmp_path / "a", tmp_path / "b"
+    line = _plain(tmp_path, ["--dump-outputs", str(d1)])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["unit"] == "Mpixels/s" and line["higher_is_better"] is True and line["dtype"] == "f64+f32 (u8 I/O)"
+    assert abs(line["value"] - F * H * W / (line["ms_per_step"] * 1e-3) / 1e6) <= 0.01 * line["value"]
+    for k in ("embed_work_sample", "parity_sample", "lapack_route_sample", "exact_route_check", "cpu_baseline",
+              "cpu_baseline_reference_model"):
+        assert line[k] is None, k
+    assert line["roofline"]["torch_copy_measured_GBs"] is None
+    frames = O.synth_bytes(0x5EED0001, 0, F, H * W * 3).reshape(F, H, W, 3)
+    tile = O.synth_bytes(0x5EED0002, 0, 1, (H // B) * (W // B)).reshape(H // B, W // B)
+    ref = O.embed_batch(frames, tile, B, A, 1)
+    out, tiles = np.load(d1 / "embed_out.npy"), np.load(d1 / "extract_tiles.npy")
+    assert out.dtype == np.float32 and tiles.dtype == np.float32
+    assert np.array_equal(out, ref) and np.array_equal(tiles, O.extract_batch(ref, frames, B, A, 1))
+    _plain(tmp_path, ["--dump-outputs", str(d2)])
+    for name in ("embed_out.npy", "extract_tiles.npy"):
+        assert (d1 / name).read_bytes() == (d2 / name).read_bytes()
+
+
+def test_dump_outputs_samples_large_arrays(tmp_path, monkeypatch):
+    """An array above its element budget is written as a seeded sample of every frame: (n, k)
+    float32, each value the frame's element at the drawn position, identical from call to call."""
+    import torch
+
+    monkeypatch.setitem(bench.DUMP_ELEMS, "embed_out", 40)
+    monkeypatch.setitem(bench.DUMP_ELEMS, "extract_tiles", 1 << 10)
+    out = torch.from_numpy(O.synth_bytes(7, 0, 5, 6 * 7 * 3).reshape(5, 6, 7, 3))
+    tiles = torch.from_numpy(O.synth_bytes(8, 0, 5, 6).reshape(5, 2, 3))
+    bench.dump_outputs(str(tmp_path / "a"), {"embed_out": out, "extract_tiles": tiles})
+    bench.dump_outputs(str(tmp_path / "b"), {"embed_out": out, "extract_tiles": tiles}, rank=1, world=2)
+    a = np.load(tmp_path / "a" / "embed_out.npy")
+    assert a.shape == (5, 8) and a.dtype == np.float32
+    pos = np.random.default_rng(bench.DUMP_SEED).integers(0, 6 * 7 * 3, size=(5, 8), dtype=np.int64)
+    assert np.array_equal(a, np.take_along_axis(out.numpy().reshape(5, -1), pos, 1))
+    assert np.array_equal(np.load(tmp_path / "a" / "extract_tiles.npy"), tiles.numpy())
+    assert np.array_equal(np.load(tmp_path / "b" / "embed_out.rank1.npy"), a)

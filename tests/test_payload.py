@@ -173,3 +173,29 @@ def test_app_round_trip_through_the_watermark(b, alpha):
     assert got == enc
     assert E.decrypt_watermark(got, key) == b"ThatsMyFace"
     assert Q.decode_tiles(np.stack([ext, ext])) == [base64.b64encode(enc)] * 2
+
+
+@pytest.mark.parametrize("iv", ["e7f38bf0781f3b112eb2d13459dbb502", 1119, 1236])
+def test_app_round_trip_ivs_whose_tile_misses_otsu_threshold(iv):
+    """The loop above at b = 16 (a 45-module symbol in 68 tile pixels) with IVs that
+    encrypt_watermark's random draw produced and whose extracted tile does not decode at Otsu's
+    threshold (it decodes at every threshold below about 0.45 of the way between Otsu's class
+    means and at none above): a recorded IV and two of the 5 in 300 seeded draws that failed,
+    one of them the narrowest (thresholds up to 60 of 158).  tmfwm_qr_decode's further
+    thresholds between the class means read them."""
+    from lapack_path import photo_cover
+
+    key = bytes(range(100, 132))
+    iv = bytes.fromhex(iv) if isinstance(iv, str) else np.random.default_rng(iv).integers(0, 256, 16, dtype=np.uint8).tobytes()
+    enc = iv + E.aes_cbc_encrypt(key, iv, E.pad(b"ThatsMyFace"))
+    buf = io.BytesIO()
+    Q.text_to_qrcode(enc).save(buf, format="PNG")
+    wm = np.asarray(Image.open(io.BytesIO(buf.getvalue())).convert("L"))
+    H, W, b, alpha = 1088, 1920, 16, 0.1
+    cov = photo_cover(H, W, 9)
+    tile = O.prepare_tile(wm, H // b, W // b, True)
+    ext = O.extract_frame(O.embed_frame(cov, tile, b, alpha), cov, b, alpha)
+    got = Q.qrcode_to_text(Image.fromarray(ext))
+    assert got == enc
+    assert E.decrypt_watermark(got, key) == b"ThatsMyFace"
+    assert Q.decode_tiles(np.stack([ext, ext])) == [base64.b64encode(enc)] * 2

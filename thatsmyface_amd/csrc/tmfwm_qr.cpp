@@ -20,7 +20,8 @@
 // image: the bytes are pinned only by the standard and round trips -- "parity unpinned".)
 //
 // The decoder is for what the app feeds it: an axis-aligned QR image (the extracted tile,
-// extract_watermark :288-292) -- global Otsu threshold, finder patterns by 1:1:3:1:1 run
+// extract_watermark :288-292) -- global Otsu threshold (then four thresholds between its class
+// means if nothing decodes at it, tmfwm_qr_decode), finder patterns by 1:1:3:1:1 run
 // ratios along rows and columns, an affine module grid from the three finder centres,
 // format information from either copy (nearest valid BCH word, <= 3 bit errors),
 // Reed-Solomon error correction per block (Berlekamp-Massey, Chien, Forney), then the
@@ -493,7 +494,7 @@ struct Pt {
     double x, y;
 };
 
-int otsu(const uint8_t *g, int h, int w, int64_t stride)
+int otsu(const uint8_t *g, int h, int w, int64_t stride, double *mean_dark = nullptr, double *mean_light = nullptr)
 {
     int64_t hist[256] = {};
     for (int y = 0; y < h; ++y)
@@ -513,6 +514,8 @@ int otsu(const uint8_t *g, int h, int w, int64_t stride)
         if (v > best) {
             best = v;
             thr = t;
+            if (mean_dark) *mean_dark = mb;
+            if (mean_light) *mean_light = mf;
         }
     }
     return thr;  // dark iff value <= thr
@@ -997,12 +1000,29 @@ int tmfwm_qr_decode(const uint8_t *gray, int32_t height, int32_t width, int64_t 
     if (len_out) *len_out = 0;
     if (!gray || height <= 0 || width <= 0 || row_stride < width || !len_out)
         return report(TMFWM_ERR_INVALID, "bad image arguments");
-    const int thr = otsu(gray, height, width, row_stride);
+    double md = -1, ml = -1;
+    const int thr0 = otsu(gray, height, width, row_stride, &md, &ml);
     Bin b{height, width, std::vector<uint8_t>((size_t)height * width)};
-    for (int y = 0; y < height; ++y)
-        for (int x = 0; x < width; ++x) b.d[(size_t)y * width + x] = gray[y * row_stride + x] <= thr;
     std::vector<uint8_t> payload;
-    if (!decode_bin(b, payload)) return report(TMFWM_ERR_NODATA, "no decodable QR code in the %dx%d image", width, height);
+    // Otsu's threshold first; if nothing decodes there, thresholds at 3/8, 5/8, 1/4 and 3/4 of the
+    // way between its two class means.  An extracted tile is not the two-level image Otsu assumes:
+    // extraction clips the dark modules to 0 and maps the resampled symbol's grey edge pixels
+    // non-linearly, and at 1.5 tile pixels per module (a 45-module symbol in 68 pixels) the edge
+    // pixels decide -- such tiles decode at every threshold below Otsu's and at none above it.
+    const double fracs[5] = {-1, 0.375, 0.625, 0.25, 0.75};
+    bool found = false;
+    for (int a = 0; a < 5 && !found; ++a) {
+        int thr = thr0;
+        if (a > 0) {
+            if (md < 0 || ml <= md) break;
+            thr = (int)(md + (ml - md) * fracs[a]);
+            if (thr == thr0) continue;
+        }
+        for (int y = 0; y < height; ++y)
+            for (int x = 0; x < width; ++x) b.d[(size_t)y * width + x] = gray[y * row_stride + x] <= thr;
+        found = decode_bin(b, payload);
+    }
+    if (!found) return report(TMFWM_ERR_NODATA, "no decodable QR code in the %dx%d image", width, height);
     *len_out = (int32_t)payload.size();
     if (!out || capacity < (int32_t)payload.size()) return report(TMFWM_ERR_INVALID, "payload of %zu bytes exceeds the buffer", payload.size());
     std::memcpy(out, payload.data(), payload.size());

@@ -16,7 +16,7 @@ OUT="$ROOT/gpurun_out/$TAG"
 LIB="$ROOT/thatsmyface_amd/libtmfwm.so"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 python3 "$ROOT/bench.py" > "$OUT/bench.log" 2>&1
+timeout -k 10 600 python3 "$ROOT/bench.py" --full > "$OUT/bench.log" 2>&1
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- \
     python3 "$ROOT/bench.py" --no-cpu-baseline > "$OUT/trace.log" 2>&1
 "$ROOT/tools/pmc_embed.sh" "$LIB" "$OUT/pmc_b8" 8 16
