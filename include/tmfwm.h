@@ -176,6 +176,23 @@ int tmfwm_embed_px(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_frame_
                    int32_t width, const uint8_t *wm_tile, int32_t block, double alpha, uint8_t *out, int32_t out_pixel_bytes,
                    int64_t out_frame_stride, int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
 
+/*
+ * tmfwm_embed_px with one watermark tile per frame (added within ABI 10; the version number is
+ * unchanged and existing entry points keep their behaviour): frame f is embedded with the
+ * (height/block) x (width/block) tile at wm_tiles + f * tile_stride.  tile_stride = 0 is one tile
+ * shared by every frame: exactly tmfwm_embed_px, which is this call with stride 0.  Any other
+ * stride must be >= (height/block)*(width/block) (padded tiles are allowed; a smaller or
+ * negative stride returns TMFWM_ERR_INVALID).  With TMFWM_MEM_HOST the n_frames tiles are
+ * staged in one copy.  With TMFWM_MEM_DEVICE `out` must not overlap `rgb` nor the tiles' whole
+ * span (n_frames - 1) * tile_stride + one tile.  Everything else -- pixel layouts, the frame
+ * strides (one stride for 3 -> 3), block sizes, routes, *n_lapack_blocks -- as tmfwm_embed_px.
+ * Extract takes no tile and has no counterpart.
+ */
+int tmfwm_embed_tiles(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_frame_stride, int64_t n_frames, int32_t height,
+                      int32_t width, const uint8_t *wm_tiles, int64_t tile_stride, int32_t block, double alpha, uint8_t *out,
+                      int32_t out_pixel_bytes, int64_t out_frame_stride, int32_t mem_kind, void *hip_stream, int32_t route,
+                      int64_t *n_lapack_blocks);
+
 /* tmfwm_extract_route with a pixel layout and frame stride per input image (ABI 8). */
 int tmfwm_extract_px(const uint8_t *wm_rgb, int32_t wm_pixel_bytes, int64_t wm_frame_stride, const uint8_t *orig_rgb,
                      int32_t orig_pixel_bytes, int64_t orig_frame_stride, int64_t n_frames, int32_t height, int32_t width,
@@ -213,6 +230,18 @@ int tmfwm_embed_multi_route(const uint8_t *rgb, int64_t n_frames, int32_t height
 int tmfwm_extract_multi_route(const uint8_t *wm_rgb, const uint8_t *orig_rgb, int64_t n_frames, int32_t height, int32_t width,
                               int64_t frame_stride, int32_t block, double alpha, uint8_t *out_tiles, const int32_t *devices,
                               int32_t n_shards, int32_t route, int64_t *n_lapack_blocks);
+
+/*
+ * tmfwm_embed_multi_route with one watermark tile per frame (added within ABI 10): frame f's
+ * tile is the host buffer wm_tiles + f * tile_stride (tile_stride >= (height/block)*(width/block);
+ * 0 is the shared tile of tmfwm_embed_multi_route, broadcast as described above).  In per-frame
+ * mode nothing is broadcast and librccl is not needed: every pass of a shard uploads the tiles
+ * of its own frames with those frames (1/192 of their bytes at block = 8), so a device only
+ * ever receives the tiles of the frames it embeds.
+ */
+int tmfwm_embed_multi_tiles(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
+                            const uint8_t *wm_tiles, int64_t tile_stride, int32_t block, double alpha, uint8_t *out,
+                            const int32_t *devices, int32_t n_shards, int32_t route, int64_t *n_lapack_blocks);
 
 /* Frees the device staging buffers the multi-GPU calls keep between calls (at most four free
  * buffers per device are kept; ABI 9).  Returns the number of buffers freed. */
@@ -286,6 +315,20 @@ int tmfwm_synth_frames(uint64_t seed, int64_t frame0, int64_t n_frames, int64_t 
  */
 int tmfwm_prepare_tile(const uint8_t *wm, int32_t wm_height, int32_t wm_width, int32_t tile_height, int32_t tile_width,
                        int32_t preserve_ratio, uint8_t *tile, int32_t mem_kind, void *hip_stream);
+
+/*
+ * tmfwm_prepare_tile for a batch (added within ABI 10): n_wm grey watermarks of one size
+ * (text_to_qrcode always renders 300 x 300), wm_stride bytes apart (>= wm_height*wm_width), to
+ * n_wm tiles tile_stride bytes apart (>= tile_height*tile_width; the bytes between padded tiles
+ * are not written).  One set of resample tables is built and uploaded for the whole batch and
+ * each resample pass is one launch over all the watermarks (groups of 1024), the white canvas
+ * and centred paste of preserve_ratio included; a tile of the watermark's own size is a copy.
+ * There is no host round trip per tile: the stream is synchronised once, at the end.  Every
+ * tile's bytes are tmfwm_prepare_tile's, which is this call with n_wm = 1.
+ */
+int tmfwm_prepare_tiles(const uint8_t *wm, int64_t n_wm, int32_t wm_height, int32_t wm_width, int64_t wm_stride,
+                        int32_t tile_height, int32_t tile_width, int32_t preserve_ratio, uint8_t *tiles, int64_t tile_stride,
+                        int32_t mem_kind, void *hip_stream);
 
 /*
  * The watermark's payload, host-side C++ (no GPU, no torch): the QR codec

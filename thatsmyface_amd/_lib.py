@@ -28,7 +28,7 @@ ERR_NODATA = -61
 
 ROUTE_HYBRID = 0  # TMFWM_ROUTE_*: the SVD route of embed / extract (include/tmfwm.h)
 ROUTE_REFERENCE = 1
-ROUTE_RANK1 = 2  # ABI 10: the hybrid route behind the rank-1 pre-pass (embed at b = 8, 16; photo mode)
+ROUTE_RANK1 = 2  # ABI 10: the hybrid route behind the rank-1 pre-pass (embed at b = 4..16 even; photo mode)
 ROUTE_RANK1_REFERENCE = 3  # ABI 10: the rank-1 pre-pass in front of the dgesdd route (no Jacobi, no K)
 ROUTES = {"hybrid": ROUTE_HYBRID, "reference": ROUTE_REFERENCE, "rank1": ROUTE_RANK1, "rank1_reference": ROUTE_RANK1_REFERENCE}
 
@@ -72,11 +72,13 @@ SIGNATURES = {
     "tmfwm_embed_route": (ctypes.c_int, [_VP, _I64, _I32, _I32, _I64, _VP, _I32, _D, _VP, _I32, _VP, _I32, _VP]),
     "tmfwm_extract_route": (ctypes.c_int, [_VP, _VP, _I64, _I32, _I32, _I64, _I32, _D, _VP, _I32, _VP, _I32, _VP]),
     "tmfwm_embed_px": (ctypes.c_int, [_VP, _I32, _I64, _I64, _I32, _I32, _VP, _I32, _D, _VP, _I32, _I64, _I32, _VP, _I32, _VP]),
+    "tmfwm_embed_tiles": (ctypes.c_int, [_VP, _I32, _I64, _I64, _I32, _I32, _VP, _I64, _I32, _D, _VP, _I32, _I64, _I32, _VP, _I32, _VP]),
     "tmfwm_extract_px": (ctypes.c_int, [_VP, _I32, _I64, _VP, _I32, _I64, _I64, _I32, _I32, _I32, _D, _VP, _I32, _VP, _I32, _VP]),
     "tmfwm_embed_multi": (ctypes.c_int, [_VP, _I64, _I32, _I32, _I64, _VP, _I32, _D, _VP, _VP, _I32, _VP]),
     "tmfwm_release_cached_buffers": (ctypes.c_int, []),
     "tmfwm_extract_multi": (ctypes.c_int, [_VP, _VP, _I64, _I32, _I32, _I64, _I32, _D, _VP, _VP, _I32, _VP]),
     "tmfwm_embed_multi_route": (ctypes.c_int, [_VP, _I64, _I32, _I32, _I64, _VP, _I32, _D, _VP, _VP, _I32, _I32, _VP]),
+    "tmfwm_embed_multi_tiles": (ctypes.c_int, [_VP, _I64, _I32, _I32, _I64, _VP, _I64, _I32, _D, _VP, _VP, _I32, _I32, _VP]),
     "tmfwm_extract_multi_route": (ctypes.c_int, [_VP, _VP, _I64, _I32, _I32, _I64, _I32, _D, _VP, _VP, _I32, _I32, _VP]),
     "tmfwm_rgb_to_ycbcr": (ctypes.c_int, [_VP, _I64, _VP, _I32, _VP]),
     "tmfwm_ycbcr_to_rgb": (ctypes.c_int, [_VP, _I64, _VP, _I32, _VP]),
@@ -88,6 +90,7 @@ SIGNATURES = {
     "tmfwm_lapack_nrm2": (ctypes.c_int, [_VP, _I64, _I32, _I32, _VP, _I32, _VP]),
     "tmfwm_synth_frames": (ctypes.c_int, [ctypes.c_uint64, _I64, _I64, _I64, _VP, _VP]),
     "tmfwm_prepare_tile": (ctypes.c_int, [_VP, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _VP]),
+    "tmfwm_prepare_tiles": (ctypes.c_int, [_VP, _I64, _I32, _I32, _I64, _I32, _I32, _I32, _VP, _I64, _I32, _VP]),
     "tmfwm_qr_encode": (ctypes.c_int, [_VP, _I32, _I32, _I32, _I32, _VP, _I32, _VP]),
     "tmfwm_qr_decode": (ctypes.c_int, [_VP, _I32, _I32, _I64, _VP, _I32, _VP]),
     "tmfwm_qr_decode_batch": (ctypes.c_int, [_VP, _I64, _I32, _I32, _VP, _I32, _VP]),

@@ -47,7 +47,8 @@ def embed_list_pass(block: int) -> bool:
 def embed_batch(frames: torch.Tensor, wm_tile: torch.Tensor, block: int = 8, alpha: float = 0.1,
                 out: torch.Tensor | None = None, stream=None, stats: dict | None = None,
                 route: str = "hybrid") -> torch.Tensor:
-    """Embed one watermark tile into every frame (watermarking.py:135 per frame).
+    """Embed one watermark tile into every frame (watermarking.py:135 per frame), or one tile
+    per frame: wm_tile is (H/b, W/b), shared, or (N, H/b, W/b), frame f getting wm_tile[f].
     stats (optional dict) receives "lapack_blocks": the blocks redone on the dgesdd route;
     asking for it synchronises the stream.  route: "hybrid" (Jacobi + the dgesdd route for
     the flagged blocks, the throughput route) or "reference" (the dgesdd route for every
@@ -56,8 +57,9 @@ def embed_batch(frames: torch.Tensor, wm_tile: torch.Tensor, block: int = 8, alp
     n, h, w, _ = frames.shape
     if block not in SUPPORTED_BLOCK_SIZES:
         raise NotImplementedError(f"block {block}")
-    if tuple(wm_tile.shape) != (h // block, w // block) or wm_tile.dtype != torch.uint8 or not wm_tile.is_cuda:
-        raise ValueError(f"wm_tile must be ({h // block}, {w // block}) uint8 on the GPU, got {tuple(wm_tile.shape)}")
+    nbh, nbw = h // block, w // block
+    if tuple(wm_tile.shape) not in ((nbh, nbw), (n, nbh, nbw)) or wm_tile.dtype != torch.uint8 or not wm_tile.is_cuda:
+        raise ValueError(f"wm_tile must be ({nbh}, {nbw}) or ({n}, {nbh}, {nbw}) uint8 on the GPU, got {tuple(wm_tile.shape)}")
     wm_tile = wm_tile.contiguous()
     if out is None:
         out = torch.empty_like(frames)
@@ -68,9 +70,14 @@ def embed_batch(frames: torch.Tensor, wm_tile: torch.Tensor, block: int = 8, alp
     cnt, ptr = _count_ptr(stats)
     with torch.cuda.device(frames.device):
         L = _lib.load()
-        _lib.check(L.tmfwm_embed_route(frames.data_ptr(), n, h, w, h * w * 3, wm_tile.data_ptr(), block, float(alpha),
-                                       out.data_ptr(), _lib.MEM_DEVICE, _stream(stream), _lib.route_code(route), ptr),
-                   "embed_batch")
+        if wm_tile.dim() == 2:
+            rc = L.tmfwm_embed_route(frames.data_ptr(), n, h, w, h * w * 3, wm_tile.data_ptr(), block, float(alpha),
+                                     out.data_ptr(), _lib.MEM_DEVICE, _stream(stream), _lib.route_code(route), ptr)
+        else:  # one tile per frame, nbh * nbw bytes apart
+            rc = L.tmfwm_embed_tiles(frames.data_ptr(), _lib.PIX_RGB, h * w * 3, n, h, w, wm_tile.data_ptr(), nbh * nbw, block,
+                                     float(alpha), out.data_ptr(), _lib.PIX_RGB, h * w * 3, _lib.MEM_DEVICE, _stream(stream),
+                                     _lib.route_code(route), ptr)
+        _lib.check(rc, "embed_batch")
     if stats is not None:
         stats["lapack_blocks"] = int(cnt.value)
         stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks())
@@ -223,4 +230,27 @@ def prepare_tile(watermark_l: torch.Tensor, tile_height: int, tile_width: int, p
         _lib.check(L.tmfwm_prepare_tile(watermark_l.data_ptr(), watermark_l.shape[0], watermark_l.shape[1], tile_height,
                                         tile_width, int(bool(preserve_ratio)), out.data_ptr(), _lib.MEM_DEVICE, _stream(stream)),
                    "prepare_tile")
+    return out
+
+
+def prepare_tiles(watermarks_l: torch.Tensor, tile_height: int, tile_width: int, preserve_ratio: bool = False,
+                  out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """prepare_tile for a batch: (N, h, w) uint8 grey watermarks of one size on the GPU ->
+    (N, tile_height, tile_width) tiles, tile i the bytes of prepare_tile(watermarks_l[i], ...).
+    One table upload and one launch per resample pass for the whole batch; synchronises the
+    stream once (the resample tables come from the host)."""
+    if not watermarks_l.is_cuda or watermarks_l.dtype != torch.uint8 or watermarks_l.dim() != 3:
+        raise ValueError("watermarks_l must be a (N, h, w) uint8 GPU tensor")
+    watermarks_l = watermarks_l.contiguous()
+    n, h, w = watermarks_l.shape
+    if out is None:
+        out = torch.empty((n, tile_height, tile_width), dtype=torch.uint8, device=watermarks_l.device)
+    elif (tuple(out.shape) != (n, tile_height, tile_width) or out.dtype != torch.uint8 or not out.is_contiguous()
+          or out.device != watermarks_l.device):
+        raise ValueError("out must be a contiguous (N, tile_height, tile_width) uint8 tensor on the watermarks' device")
+    with torch.cuda.device(watermarks_l.device):
+        L = _lib.load()
+        _lib.check(L.tmfwm_prepare_tiles(watermarks_l.data_ptr(), n, h, w, h * w, tile_height, tile_width,
+                                         int(bool(preserve_ratio)), out.data_ptr(), tile_height * tile_width, _lib.MEM_DEVICE,
+                                         _stream(stream)), "prepare_tiles")
     return out

@@ -312,7 +312,6 @@ TMF_DEVI void embed_blocks(const EmbedArgs &a, const StripPos &pos, uint32_t id,
     uint32_t (*pix)[64] = reinterpret_cast<uint32_t (*)[64]>(lds2);
     const uint8_t *src = a.src + pos.frame * a.frame_stride;
     uint8_t *dst = a.dst + pos.frame * a.frame_stride;
-
     TMF_STAMP_INIT;
     float x[R][B];
     {
@@ -449,7 +448,8 @@ TMF_DEVI void embed_blocks(const EmbedArgs &a, const StripPos &pos, uint32_t id,
 
     // N7 blend (:198): S[0] = f32(f64(S[0]) + alpha * (w / 255.0)), S[0] the largest; as
     // intervals [f32(max(sigma - Es, 0)), f32(sigma + Es)] blended at both ends
-    const uint32_t wv = pos.valid ? a.wm[(int64_t)pos.bi * a.nbw + pos.bj] : 0u;
+    // (frame f's tile at a.wm + f * a.wm_stride; stride 0: one tile for every frame)
+    const uint32_t wv = pos.valid ? a.wm[pos.frame * a.wm_stride + (int64_t)pos.bi * a.nbw + pos.bj] : 0u;
     const double cw = a.alpha * ((double)wv / 255.0);
     float Sl[B], Sh[B];
     bool neg = false;  // alpha < 0 pushing S'[0] below zero: outside the certificate's S' >= 0

@@ -152,6 +152,33 @@ bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
 
 size_t span_bytes(int64_t n, int64_t stride, int64_t frame_bytes) { return n == 0 ? 0 : (size_t)((n - 1) * stride + frame_bytes); }
 
+// tile_stride of the per-frame-tile calls: 0 (one shared tile) or at least a tile (padded tiles are allowed)
+int check_tile_stride(int64_t tile_stride, int64_t tbytes)
+{
+    if (tile_stride < 0 || (tile_stride != 0 && tile_stride < tbytes))
+        return fail(TMFWM_ERR_INVALID, "tile_stride %lld: 0 (one shared tile) or >= (H/block)*(W/block) = %lld", (long long)tile_stride,
+                    (long long)tbytes);
+    return 0;
+}
+
+// Host tiles (tile_stride apart; 0: one tile) staged into `buf` in one copy, compact; *dstride is
+// the stride the kernels then use.
+int stage_tiles(const uint8_t *tiles, int64_t n, int64_t tile_stride, size_t tbytes, hipStream_t st, DevBuf &buf, const uint8_t **dev,
+                int64_t *dstride)
+{
+    const size_t nt = tile_stride ? (size_t)n : 1;
+    if (int rc = buf.alloc(tbytes * nt, st, "watermark tiles")) return rc;
+    if (tbytes) {
+        if (nt == 1 || tile_stride == (int64_t)tbytes)
+            TMF_HIP(hipMemcpyAsync(buf.p, tiles, tbytes * nt, hipMemcpyHostToDevice, st));
+        else
+            TMF_HIP(hipMemcpy2DAsync(buf.p, tbytes, tiles, (size_t)tile_stride, tbytes, nt, hipMemcpyHostToDevice, st));
+    }
+    *dev = static_cast<const uint8_t *>(buf.p);
+    *dstride = tile_stride ? (int64_t)tbytes : 0;
+    return 0;
+}
+
 // Second-pass bookkeeping: frames go in chunks of at most kListCap
 // blocks (and 65535 frames, the grid's y limit); each chunk's first pass appends the
 // blocks that need the dgesdd route to one shared id list (u32, chunk-relative) and
@@ -318,6 +345,7 @@ int run_embed(EmbedArgs a, hipStream_t st, int64_t *n_lapack, bool check, uint32
         k.nframes = a.nframes - f0 < ch.frames ? a.nframes - f0 : ch.frames;
         k.src = a.src + f0 * a.frame_stride;
         k.dst = a.dst + f0 * a.frame_stride;
+        k.wm = a.wm + f0 * a.wm_stride;  // the lists' block ids are relative to the chunk: so is its first tile
         k.fb_list = static_cast<uint32_t *>(list.p);
         k.fb_count = static_cast<uint32_t *>(counts.p) + c;
         k.fb_bad = static_cast<uint32_t *>(counts.p) + ch.n + c;
@@ -435,8 +463,8 @@ int64_t count_chunks(int64_t nframes, int H, int W, int block)
     return ch.n;
 }
 
-int embed_device_async(const uint8_t *src, int64_t n, int H, int W, int64_t stride, const uint8_t *tile, int block,
-                       double alpha, uint8_t *dst, hipStream_t st, uint32_t *sink, int route)
+int embed_device_async(const uint8_t *src, int64_t n, int H, int W, int64_t stride, const uint8_t *tile, int64_t tile_stride,
+                       int block, double alpha, uint8_t *dst, hipStream_t st, uint32_t *sink, int route)
 {
     if (int rc = ::check_frames(n, H, W, stride, block)) return rc;
     if (n == 0 || H == 0 || W == 0) {
@@ -447,6 +475,7 @@ int embed_device_async(const uint8_t *src, int64_t n, int H, int W, int64_t stri
     a.src = src;
     a.dst = dst;
     a.wm = tile;
+    a.wm_stride = tile_stride;
     a.aligned = dev_aligned(src, dst, stride, W);
     return run_embed(a, st, nullptr, false, sink, route);
 }
@@ -490,9 +519,11 @@ int tmfwm_device_count(void)
     return n;
 }
 
-int tmfwm_embed_route(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
-                      const uint8_t *wm_tile, int32_t block, double alpha, uint8_t *out, int32_t mem_kind, void *hip_stream,
-                      int32_t route, int64_t *n_lapack_blocks)
+// 3-byte pixels in and out, one frame stride (tmfwm_embed_route; tmfwm_embed_tiles' 3 -> 3 case):
+// frame f's tile at wm_tile + f * tile_stride (0: one tile for every frame)
+static int embed_rgb(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
+                     const uint8_t *wm_tile, int64_t tile_stride, int32_t block, double alpha, uint8_t *out, int32_t mem_kind,
+                     void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
 {
     t_err.clear();
     if (route < TMFWM_ROUTE_HYBRID || route > TMFWM_ROUTE_RANK1_REFERENCE) return fail(TMFWM_ERR_INVALID, "route %d", route);
@@ -501,12 +532,14 @@ int tmfwm_embed_route(const uint8_t *rgb, int64_t n_frames, int32_t height, int3
         t_list_pass = 0;  // this call's count from here on (an early return leaves 0)
     }
     if (int rc = check_frames(n_frames, height, width, frame_stride, block)) return rc;
+    const int nbh = height / block, nbw = width / block;
+    if (int rc = check_tile_stride(tile_stride, (int64_t)nbh * nbw)) return rc;
     if (!std::isfinite(alpha)) return fail(TMFWM_ERR_INVALID, "alpha is not finite");
     if (int rc = need_device()) return rc;
     if (n_frames == 0 || height == 0 || width == 0) return 0;
-    const int nbh = height / block, nbw = width / block;
     const int64_t fbytes = (int64_t)height * width * 3;
     const size_t span = span_bytes(n_frames, frame_stride, fbytes), tbytes = (size_t)nbh * nbw;
+    const size_t tspan = span_bytes(n_frames, tile_stride, (int64_t)tbytes);  // every frame's tile
     hipStream_t st = pick_stream(hip_stream);
     tmf::EmbedArgs a = tmf::embed_args(n_frames, height, width, frame_stride, block, alpha);
     if (mem_kind == TMFWM_MEM_DEVICE) {
@@ -516,10 +549,11 @@ int tmfwm_embed_route(const uint8_t *rgb, int64_t n_frames, int32_t height, int3
             if (int rc = check_device_ptr(wm_tile, "wm_tile")) return rc;
         }
         if (ranges_overlap(rgb, span, out, span)) return fail(TMFWM_ERR_INVALID, "out overlaps rgb (in-place embed is not supported)");
-        if (tbytes && ranges_overlap(wm_tile, tbytes, out, span)) return fail(TMFWM_ERR_INVALID, "out overlaps wm_tile");
+        if (tbytes && ranges_overlap(wm_tile, tspan, out, span)) return fail(TMFWM_ERR_INVALID, "out overlaps wm_tile");
         a.src = rgb;
         a.dst = out;
         a.wm = wm_tile;
+        a.wm_stride = tile_stride;
         a.aligned = tmf::dev_aligned(rgb, out, frame_stride, width);
         return tmf::run_embed(a, st, n_lapack_blocks, false, nullptr, route);
     }
@@ -528,12 +562,10 @@ int tmfwm_embed_route(const uint8_t *rgb, int64_t n_frames, int32_t height, int3
     DevBuf din, dout, dwm;
     if (int rc = din.alloc(span, st, "input frames")) return rc;
     if (int rc = dout.alloc(span, st, "output frames")) return rc;
-    if (int rc = dwm.alloc(tbytes, st, "watermark tile")) return rc;
     TMF_HIP(hipMemcpyAsync(din.p, rgb, span, hipMemcpyHostToDevice, st));
-    if (tbytes) TMF_HIP(hipMemcpyAsync(dwm.p, wm_tile, tbytes, hipMemcpyHostToDevice, st));
+    if (int rc = stage_tiles(wm_tile, n_frames, tile_stride, tbytes, st, dwm, &a.wm, &a.wm_stride)) return rc;
     a.src = static_cast<const uint8_t *>(din.p);
     a.dst = static_cast<uint8_t *>(dout.p);
-    a.wm = static_cast<const uint8_t *>(dwm.p);
     a.aligned = frame_stride % 4 == 0 && width % 4 == 0;
     const int64_t nch = tmf::count_chunks(n_frames, height, width, block);
     HostSink sink(nch, st);
@@ -547,6 +579,14 @@ int tmfwm_embed_route(const uint8_t *rgb, int64_t n_frames, int32_t height, int3
     }
     TMF_HIP(hipStreamSynchronize(st));
     return sink.p ? tmf::sum_sink(sink.p, nch, n_lapack_blocks) : 0;
+}
+
+int tmfwm_embed_route(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
+                      const uint8_t *wm_tile, int32_t block, double alpha, uint8_t *out, int32_t mem_kind, void *hip_stream,
+                      int32_t route, int64_t *n_lapack_blocks)
+{
+    return embed_rgb(rgb, n_frames, height, width, frame_stride, wm_tile, 0, block, alpha, out, mem_kind, hip_stream, route,
+                     n_lapack_blocks);
 }
 
 int tmfwm_embed_ex(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
@@ -672,15 +712,17 @@ int device_rgb(const uint8_t *src, int32_t px, int64_t stride, int64_t n, int32_
 }  // namespace
 }  // extern "C++"
 
-int tmfwm_embed_px(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_frame_stride, int64_t n_frames, int32_t height,
-                   int32_t width, const uint8_t *wm_tile, int32_t block, double alpha, uint8_t *out, int32_t out_pixel_bytes,
-                   int64_t out_frame_stride, int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+int tmfwm_embed_tiles(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_frame_stride, int64_t n_frames, int32_t height,
+                      int32_t width, const uint8_t *wm_tiles, int64_t tile_stride, int32_t block, double alpha, uint8_t *out,
+                      int32_t out_pixel_bytes, int64_t out_frame_stride, int32_t mem_kind, void *hip_stream, int32_t route,
+                      int64_t *n_lapack_blocks)
 {
     t_err.clear();
+    const uint8_t *wm_tile = wm_tiles;
     if (in_pixel_bytes == TMFWM_PIX_RGB && out_pixel_bytes == TMFWM_PIX_RGB) {
         if (in_frame_stride != out_frame_stride) return fail(TMFWM_ERR_INVALID, "3-byte input and output need one frame_stride");
-        return tmfwm_embed_route(rgb, n_frames, height, width, in_frame_stride, wm_tile, block, alpha, out, mem_kind, hip_stream,
-                                 route, n_lapack_blocks);
+        return embed_rgb(rgb, n_frames, height, width, in_frame_stride, wm_tile, tile_stride, block, alpha, out, mem_kind, hip_stream,
+                         route, n_lapack_blocks);
     }
     if (route < TMFWM_ROUTE_HYBRID || route > TMFWM_ROUTE_RANK1_REFERENCE) return fail(TMFWM_ERR_INVALID, "route %d", route);
     if (n_lapack_blocks) {
@@ -690,11 +732,12 @@ int tmfwm_embed_px(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_frame_
     if (int rc = check_frames(n_frames, height, width, (int64_t)height * width * 3, block)) return rc;
     if (int rc = check_px(in_pixel_bytes, in_frame_stride, height, width, "input")) return rc;
     if (int rc = check_px(out_pixel_bytes, out_frame_stride, height, width, "output")) return rc;
+    const int nbh = height / block, nbw = width / block;
+    if (int rc = check_tile_stride(tile_stride, (int64_t)nbh * nbw)) return rc;
     if (!std::isfinite(alpha)) return fail(TMFWM_ERR_INVALID, "alpha is not finite");
     if (mem_kind != TMFWM_MEM_HOST && mem_kind != TMFWM_MEM_DEVICE) return fail(TMFWM_ERR_INVALID, "mem_kind %d", mem_kind);
     if (int rc = need_device()) return rc;
     if (n_frames == 0 || height == 0 || width == 0) return 0;
-    const int nbh = height / block, nbw = width / block;
     const size_t tbytes = (size_t)nbh * nbw;
     const int64_t f3 = (int64_t)height * width * 3, fo = (int64_t)height * width * out_pixel_bytes;
     const size_t ospan = span_bytes(n_frames, out_frame_stride, fo);
@@ -705,6 +748,9 @@ int tmfwm_embed_px(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_frame_
             return fail(TMFWM_ERR_INVALID, "out overlaps rgb (in-place embed is not supported)");
         if (tbytes) {
             if (int rc = check_device_ptr(wm_tile, "wm_tile")) return rc;
+            // per-frame tiles only: with one shared tile this is tmfwm_embed_px, which never had the rule
+            if (tile_stride && ranges_overlap(wm_tile, span_bytes(n_frames, tile_stride, (int64_t)tbytes), out, ospan))
+                return fail(TMFWM_ERR_INVALID, "out overlaps wm_tile");
         }
     } else if (!out || (tbytes && !wm_tile)) {
         return fail(TMFWM_ERR_INVALID, "NULL host pointer");
@@ -716,16 +762,16 @@ int tmfwm_embed_px(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_frame_
                             &s3p, &s3))
         return rc;
     const uint8_t *wm = wm_tile;
+    int64_t wm_stride = tile_stride;
     if (mem_kind == TMFWM_MEM_HOST && tbytes) {
-        if (int rc = dwm.alloc(tbytes, st, "watermark tile")) return rc;
-        TMF_HIP(hipMemcpyAsync(dwm.p, wm_tile, tbytes, hipMemcpyHostToDevice, st));
-        wm = static_cast<const uint8_t *>(dwm.p);
+        if (int rc = stage_tiles(wm_tile, n_frames, tile_stride, tbytes, st, dwm, &wm, &wm_stride)) return rc;
     }
     if (int rc = dst3.alloc(span_bytes(n_frames, s3, f3), st, "output frames")) return rc;
     tmf::EmbedArgs a = tmf::embed_args(n_frames, height, width, s3, block, alpha);
     a.src = s3p;
     a.dst = static_cast<uint8_t *>(dst3.p);
     a.wm = wm;
+    a.wm_stride = wm_stride;
     a.aligned = tmf::dev_aligned(a.src, a.dst, s3, width);
     const int64_t nch = tmf::count_chunks(n_frames, height, width, block);
     HostSink sink(mem_kind == TMFWM_MEM_HOST ? nch : kSinkChunks + 1, st);
@@ -750,6 +796,14 @@ int tmfwm_embed_px(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_frame_
         if (sink.p) return tmf::sum_sink(sink.p, nch, n_lapack_blocks);
     }
     return 0;
+}
+
+int tmfwm_embed_px(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_frame_stride, int64_t n_frames, int32_t height,
+                   int32_t width, const uint8_t *wm_tile, int32_t block, double alpha, uint8_t *out, int32_t out_pixel_bytes,
+                   int64_t out_frame_stride, int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    return tmfwm_embed_tiles(rgb, in_pixel_bytes, in_frame_stride, n_frames, height, width, wm_tile, 0, block, alpha, out,
+                             out_pixel_bytes, out_frame_stride, mem_kind, hip_stream, route, n_lapack_blocks);
 }
 
 int tmfwm_extract_px(const uint8_t *wm_rgb, int32_t wm_pixel_bytes, int64_t wm_frame_stride, const uint8_t *orig_rgb,
@@ -1053,13 +1107,19 @@ int tmfwm_synth_frames(uint64_t seed, int64_t frame0, int64_t n_frames, int64_t 
     return 0;
 }
 
-int tmfwm_prepare_tile(const uint8_t *wm, int32_t wm_height, int32_t wm_width, int32_t tile_height, int32_t tile_width,
-                       int32_t preserve_ratio, uint8_t *tile, int32_t mem_kind, void *hip_stream)
+int tmfwm_prepare_tiles(const uint8_t *wm, int64_t n_wm, int32_t wm_height, int32_t wm_width, int64_t wm_stride,
+                        int32_t tile_height, int32_t tile_width, int32_t preserve_ratio, uint8_t *tiles, int64_t tile_stride,
+                        int32_t mem_kind, void *hip_stream)
 {
     t_err.clear();
+    if (n_wm < 0) return fail(TMFWM_ERR_INVALID, "n_wm < 0");
     if (wm_height <= 0 || wm_width <= 0 || tile_height <= 0 || tile_width <= 0)
         return fail(TMFWM_ERR_INVALID, "height and width must be > 0 (watermark %dx%d, tile %dx%d)", wm_width, wm_height,
                     tile_width, tile_height);
+    const size_t wbytes = (size_t)wm_height * wm_width, tbytes = (size_t)tile_height * tile_width;
+    if (wm_stride < (int64_t)wbytes) return fail(TMFWM_ERR_INVALID, "wm_stride %lld < wm_height*wm_width", (long long)wm_stride);
+    if (tile_stride < (int64_t)tbytes)
+        return fail(TMFWM_ERR_INVALID, "tile_stride %lld < tile_height*tile_width", (long long)tile_stride);
     if (mem_kind != TMFWM_MEM_HOST && mem_kind != TMFWM_MEM_DEVICE) return fail(TMFWM_ERR_INVALID, "mem_kind %d", mem_kind);
     // watermarking.py:105-110: ratio = min(tw/ow, th/oh); new size int(size * ratio)
     int rh = tile_height, rw = tile_width, px = 0, py = 0;
@@ -1072,38 +1132,67 @@ int tmfwm_prepare_tile(const uint8_t *wm, int32_t wm_height, int32_t wm_width, i
         px = (tile_width - rw) / 2;  // :120-121
         py = (tile_height - rh) / 2;
     }
-    if (mem_kind == TMFWM_MEM_DEVICE) {
-        if (int rc = check_device_ptr(wm, "wm")) return rc;
-        if (int rc = check_device_ptr(tile, "tile")) return rc;
-    } else if (!wm || !tile) {
-        return fail(TMFWM_ERR_INVALID, "NULL host pointer");
+    const size_t wspan = span_bytes(n_wm, wm_stride, (int64_t)wbytes), tspan = span_bytes(n_wm, tile_stride, (int64_t)tbytes);
+    if (n_wm > 0) {
+        if (mem_kind == TMFWM_MEM_DEVICE) {
+            if (int rc = check_device_ptr(wm, "wm")) return rc;
+            if (int rc = check_device_ptr(tiles, "tiles")) return rc;
+            if (ranges_overlap(wm, wspan, tiles, tspan)) return fail(TMFWM_ERR_INVALID, "tiles overlaps wm");
+        } else if (!wm || !tiles) {
+            return fail(TMFWM_ERR_INVALID, "NULL host pointer");
+        }
     }
     if (int rc = need_device()) return rc;
+    if (n_wm == 0) return 0;
     hipStream_t st = pick_stream(hip_stream);
     tmf::ResamplePlan plan;
     plan.build(wm_height, wm_width, rh, rw);
-    const std::vector<int> tables = plan.pack();
-    const size_t wbytes = (size_t)wm_height * wm_width, tbytes = (size_t)tile_height * tile_width;
+    const std::vector<int> tables = plan.pack();  // one plan, one upload for the whole batch
     DevBuf dtab, dtmp, dwm, dtile;
     if (int rc = dtab.alloc(tables.size() * sizeof(int), st, "resample tables")) return rc;
-    if (int rc = dtmp.alloc(plan.tmp_bytes(), st, "resample scratch")) return rc;
+    if (int rc = dtmp.alloc(tmf::resize_tmp_bytes(plan, n_wm), st, "resample scratch")) return rc;
     const uint8_t *src = wm;
-    uint8_t *dst = tile;
-    if (mem_kind == TMFWM_MEM_HOST) {
-        if (int rc = dwm.alloc(wbytes, st, "watermark")) return rc;
-        if (int rc = dtile.alloc(tbytes, st, "tile")) return rc;
-        TMF_HIP(hipMemcpyAsync(dwm.p, wm, wbytes, hipMemcpyHostToDevice, st));
+    uint8_t *dst = tiles;
+    int64_t sstride = wm_stride, dstride = tile_stride;
+    if (mem_kind == TMFWM_MEM_HOST) {  // staged compact: the caller's bytes between watermarks / tiles are not touched
+        sstride = (int64_t)wbytes;
+        dstride = (int64_t)tbytes;
+        if (int rc = dwm.alloc(wbytes * (size_t)n_wm, st, "watermarks")) return rc;
+        if (int rc = dtile.alloc(tbytes * (size_t)n_wm, st, "tiles")) return rc;
+        if (n_wm == 1 || wm_stride == sstride)
+            TMF_HIP(hipMemcpyAsync(dwm.p, wm, wbytes * (size_t)n_wm, hipMemcpyHostToDevice, st));
+        else
+            TMF_HIP(hipMemcpy2DAsync(dwm.p, wbytes, wm, (size_t)wm_stride, wbytes, (size_t)n_wm, hipMemcpyHostToDevice, st));
         src = static_cast<const uint8_t *>(dwm.p);
         dst = static_cast<uint8_t *>(dtile.p);
     }
     TMF_HIP(hipMemcpyAsync(dtab.p, tables.data(), tables.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    if (preserve_ratio) TMF_HIP(hipMemsetAsync(dst, 255, tbytes, st));  // Image.new("L", ..., 255) (:116)
-    TMF_HIP(tmf::launch_resize_lanczos(src, plan, static_cast<const int *>(dtab.p), static_cast<uint8_t *>(dtmp.p),
-                                       dst + (size_t)py * tile_width + px, tile_width, st));
-    if (mem_kind == TMFWM_MEM_HOST) TMF_HIP(hipMemcpyAsync(tile, dst, tbytes, hipMemcpyDeviceToHost, st));
+    if (preserve_ratio) {  // Image.new("L", ..., 255) (:116)
+        if (n_wm == 1 || dstride == (int64_t)tbytes)
+            TMF_HIP(hipMemsetAsync(dst, 255, tbytes * (size_t)n_wm, st));
+        else
+            TMF_HIP(hipMemset2DAsync(dst, (size_t)dstride, 255, tbytes, (size_t)n_wm, st));
+    }
+    TMF_HIP(tmf::launch_resize_lanczos_batch(src, sstride, n_wm, plan, static_cast<const int *>(dtab.p),
+                                             static_cast<uint8_t *>(dtmp.p), dst + (size_t)py * tile_width + px, tile_width, dstride,
+                                             st));
+    if (mem_kind == TMFWM_MEM_HOST) {
+        if (n_wm == 1 || tile_stride == dstride)
+            TMF_HIP(hipMemcpyAsync(tiles, dst, tbytes * (size_t)n_wm, hipMemcpyDeviceToHost, st));
+        else
+            TMF_HIP(hipMemcpy2DAsync(tiles, (size_t)tile_stride, dst, tbytes, tbytes, (size_t)n_wm, hipMemcpyDeviceToHost, st));
+    }
     // the host-side tables (and, for the host path, the result) must outlive the copies
     TMF_HIP(hipStreamSynchronize(st));
     return 0;
+}
+
+int tmfwm_prepare_tile(const uint8_t *wm, int32_t wm_height, int32_t wm_width, int32_t tile_height, int32_t tile_width,
+                       int32_t preserve_ratio, uint8_t *tile, int32_t mem_kind, void *hip_stream)
+{
+    // the batched call with one watermark (the size check comes before the stride checks)
+    return tmfwm_prepare_tiles(wm, 1, wm_height, wm_width, (int64_t)wm_height * wm_width, tile_height, tile_width, preserve_ratio,
+                               tile, (int64_t)tile_height * tile_width, mem_kind, hip_stream);
 }
 
 }  // extern "C"

@@ -144,7 +144,7 @@ TMF_DEVI void embed_fix_block(const EmbedArgs &a, uint32_t id, FixLds<B> &f, int
     // rounded to f32 (numpy's astype) from the route's f64 U and VT
     const double *U64 = f.ws + B * B, *VT64 = f.ws + 2 * B * B;
     float *M = f.M();
-    const double w = (double)a.wm[(int64_t)bi * a.nbw + bj];
+    const double w = (double)a.wm[fr * a.wm_stride + (int64_t)bi * a.nbw + bj];
     const float s0 = (float)((double)S[0] + a.alpha * (w / 255.0));
     for (int e = gl; e < B * B; e += G) {
         const int i = e / B, j = e % B;

@@ -24,7 +24,8 @@ __host__ __device__ inline uint32_t shard_base(uint32_t s, uint32_t rows, uint32
 struct EmbedArgs {
     const uint8_t *src;
     uint8_t *dst;
-    const uint8_t *wm;       // nbh x nbw tile, shared by all frames
+    const uint8_t *wm;       // nbh x nbw tile of frame 0
+    int64_t wm_stride;       // bytes between consecutive frames' tiles; 0: one tile shared by all frames
     int64_t nframes;
     int64_t frame_stride;    // bytes between frames (>= H*W*3)
     int H, W, block, nbh, nbw, strips_per_row;
@@ -85,8 +86,9 @@ int check_frames(int64_t n, int32_t H, int32_t W, int64_t stride, int32_t block)
 // caller sums them with sum_sink() once the stream is done.  Arguments as tmfwm_embed_ex /
 // tmfwm_extract_ex with TMFWM_MEM_DEVICE (checked the same way).
 int64_t count_chunks(int64_t nframes, int H, int W, int block);
-int embed_device_async(const uint8_t *src, int64_t n, int H, int W, int64_t stride, const uint8_t *tile, int block,
-                       double alpha, uint8_t *dst, hipStream_t st, uint32_t *sink, int route = TMFWM_ROUTE_HYBRID);
+// embed: frame f's tile at tile + f * tile_stride (0: one tile shared by all frames)
+int embed_device_async(const uint8_t *src, int64_t n, int H, int W, int64_t stride, const uint8_t *tile, int64_t tile_stride,
+                       int block, double alpha, uint8_t *dst, hipStream_t st, uint32_t *sink, int route = TMFWM_ROUTE_HYBRID);
 int extract_device_async(const uint8_t *wsrc, const uint8_t *osrc, int64_t n, int H, int W, int64_t stride, int block,
                          double alpha, uint8_t *out, hipStream_t st, uint32_t *sink, int route = TMFWM_ROUTE_HYBRID);
 int sum_sink(const uint32_t *sink, int64_t nchunks, int64_t *lapack);  // TMFWM_ERR_HIP on non-convergence
@@ -136,6 +138,12 @@ struct ResamplePlan {
 
 hipError_t launch_resize_lanczos(const uint8_t *in, const ResamplePlan &plan, const int *tables, uint8_t *tmp, uint8_t *out,
                                  int ldo, hipStream_t st);
+// n equally sized images in_stride bytes apart -> n outputs out_stride bytes apart, one plan and
+// one table upload for all of them; tmp: device scratch of resize_tmp_bytes(plan, n)
+constexpr int64_t kResizeGroup = 1024;  // images per launch
+size_t resize_tmp_bytes(const ResamplePlan &plan, int64_t n);
+hipError_t launch_resize_lanczos_batch(const uint8_t *in, int64_t in_stride, int64_t n, const ResamplePlan &plan, const int *tables,
+                                       uint8_t *tmp, uint8_t *out, int ldo, int64_t out_stride, hipStream_t st);
 hipError_t launch_synth(uint64_t seed, int64_t frame0, int64_t nframes, int64_t frame_bytes, uint8_t *out, hipStream_t st);
 
 }  // namespace tmf

@@ -1,8 +1,8 @@
 // HIP kernels of the watermark path for gfx950 (MI355X).
 //
 // Layout in HBM: frames are H x W x 3 u8, HWC-interleaved (PIL / numpy order), frame
-// i at base + i * frame_stride.  The watermark tile is (H/b) x (W/b) u8 shared by
-// every frame of a batch.  Extracted tiles are (H/b) x (W/b) u8 per frame.
+// i at base + i * frame_stride.  The watermark tile is (H/b) x (W/b) u8, frame i's
+// at wm + i * wm_stride (stride 0: one tile shared by every frame of a batch).  Extracted tiles are (H/b) x (W/b) u8 per frame.
 //
 // Work decomposition: a workgroup is ONE wave of 64 lanes that owns a
 // strip of 64/L horizontally adjacent b x b blocks of one block row of one frame;
@@ -338,6 +338,7 @@ static hipError_t launch_embed_b(EmbedArgs a, hipStream_t st)
         const int64_t nf = a.nframes - f0 < 65535 ? a.nframes - f0 : 65535;
         c.src = a.src + f0 * a.frame_stride;
         c.dst = a.dst + f0 * a.frame_stride;
+        c.wm = a.wm + f0 * a.wm_stride;
         hipLaunchKernelGGL((embed_kernel<B, false>), dim3((unsigned)gx, (unsigned)nf), dim3(64), 0, st, c);
     }
     if (kDeferMax<B> > 0 && a.slow_list) {  // the list pass over the blocks the first pass left unfinished (ids relative to a.src)

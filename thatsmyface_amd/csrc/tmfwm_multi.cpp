@@ -9,7 +9,8 @@
 // copied to the first shard's device and broadcast to every other device with RCCL
 // (ncclBroadcast over xGMI, communicators from ncclCommInitAll, cached per device set).
 // Shards that share a device (logical shards, e.g. several shards on a one-GPU box) share
-// that device's copy of the tile.
+// that device's copy of the tile.  With one tile per frame (tmfwm_embed_multi_tiles) there is
+// no exchange at all: every pass uploads its own frames' tiles with them.
 //
 // librccl is opened on first use (dlopen), so libtmfwm.so itself keeps no link-time
 // dependency on it; under torch the already-loaded librccl.so.1 is reused.
@@ -330,9 +331,12 @@ int distribute_tile(const uint8_t *wm_tile, size_t tbytes, std::vector<DeviceTil
 // (each copy call returns once its data has been staged) the kernels of one pass run while
 // the neighbouring passes move over PCIe.  The per-pass counts (dgesdd-route blocks,
 // non-convergence) land in pinned host memory and are summed once the shard is done.
+// extra_bytes per frame (the per-frame watermark tiles of tmfwm_embed_multi_tiles) lie in the
+// input slot behind the n_inputs frame regions, at din + n_inputs * (per * in_bytes); they are
+// uploaded by `up` with the frames and do not count against the slot budget.
 template <typename Up, typename Kern, typename Down>
 void run_shard(Shard &s, const DeviceTile &u, int64_t in_bytes, int64_t out_bytes, int n_inputs, int H, int W, int block,
-               Up up, Kern kern, Down down)
+               Up up, Kern kern, Down down, int64_t extra_bytes = 0)
 {
     auto fail_here = [&](int rc, const std::string &m) {
         if (s.rc == 0) {
@@ -345,7 +349,7 @@ void run_shard(Shard &s, const DeviceTile &u, int64_t in_bytes, int64_t out_byte
     if (n == 0) return;
     const int64_t per = std::min<int64_t>(n, pass_frames(in_bytes * n_inputs + out_bytes));
     const int64_t npass = (n + per - 1) / per;
-    const size_t in_slot = (size_t)(per * in_bytes * n_inputs), out_slot = (size_t)(per * out_bytes);
+    const size_t in_slot = (size_t)(per * (in_bytes * n_inputs + extra_bytes)), out_slot = (size_t)(per * out_bytes);
     const int64_t chunks_per_pass = tmf::count_chunks(per, H, W, block);  // a shorter last pass has no more
     BufCache &bc = BufCache::get();
     uint8_t *din[2] = {nullptr, nullptr}, *dout[2] = {nullptr, nullptr};
@@ -451,9 +455,13 @@ int make_streams(std::vector<Shard> &sh)
 
 extern "C" {
 
-int tmfwm_embed_multi_route(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
-                            const uint8_t *wm_tile, int32_t block, double alpha, uint8_t *out, const int32_t *devices,
-                            int32_t n_shards, int32_t route, int64_t *n_lapack_blocks)
+// tile_stride 0: one tile, broadcast to every device (tmfwm_embed_multi_route).  Otherwise frame
+// f's tile is at wm_tile + f * tile_stride: every pass uploads the tiles of its own frames behind
+// them in its input slot, so a shard receives only its frames' tiles and nothing is broadcast
+// (no RCCL in this mode).
+int tmfwm_embed_multi_tiles(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
+                            const uint8_t *wm_tile, int64_t tile_stride, int32_t block, double alpha, uint8_t *out,
+                            const int32_t *devices, int32_t n_shards, int32_t route, int64_t *n_lapack_blocks)
 {
     tmf::clear_error();
     if (n_lapack_blocks) *n_lapack_blocks = 0;
@@ -462,6 +470,9 @@ int tmfwm_embed_multi_route(const uint8_t *rgb, int64_t n_frames, int32_t height
     if (!std::isfinite(alpha)) return report(TMFWM_ERR_INVALID, "alpha is not finite");
     const int nbh = height / block, nbw = width / block;
     const size_t tbytes = (size_t)nbh * nbw;
+    if (tile_stride < 0 || (tile_stride != 0 && tile_stride < (int64_t)tbytes))
+        return report(TMFWM_ERR_INVALID, "tile_stride %lld: 0 (one shared tile) or >= (H/block)*(W/block) = %zu", (long long)tile_stride,
+                      tbytes);
     if (n_frames > 0 && (!rgb || !out || (tbytes && !wm_tile))) return report(TMFWM_ERR_INVALID, "NULL host pointer");
     std::vector<Shard> sh;
     std::vector<DeviceTile> uniq;
@@ -469,7 +480,8 @@ int tmfwm_embed_multi_route(const uint8_t *rgb, int64_t n_frames, int32_t height
     if (int rc = plan_shards(devices, n_shards, n_frames, sh, uniq)) return rc;
     if (n_frames == 0 || height == 0 || width == 0) return 0;
     if (int rc = make_streams(sh)) return rc;
-    if (int rc = distribute_tile(wm_tile, tbytes, uniq)) return rc;
+    const bool per_frame = tile_stride != 0 && tbytes != 0;
+    if (int rc = per_frame ? distribute_tile(nullptr, 0, uniq) : distribute_tile(wm_tile, tbytes, uniq)) return rc;  // events only
     const int64_t fbytes = (int64_t)height * width * 3;
     std::vector<std::thread> th;
     for (Shard &shard : sh) {
@@ -479,7 +491,15 @@ int tmfwm_embed_multi_route(const uint8_t *rgb, int64_t n_frames, int32_t height
             const DeviceTile &u = *up;
             run_shard(
                 *sp, u, fbytes, fbytes, 1, height, width, block,
-                [&](int64_t f, int64_t k, uint8_t *din, int64_t, hipStream_t st) -> int {
+                [&](int64_t f, int64_t k, uint8_t *din, int64_t half, hipStream_t st) -> int {
+                    if (per_frame) {  // the pass's tiles, compact, behind its frames
+                        const uint8_t *t = wm_tile + f * tile_stride;
+                        const hipError_t e =
+                            k == 1 || tile_stride == (int64_t)tbytes
+                                ? hipMemcpyAsync(din + half, t, (size_t)k * tbytes, hipMemcpyHostToDevice, st)
+                                : hipMemcpy2DAsync(din + half, tbytes, t, (size_t)tile_stride, tbytes, (size_t)k, hipMemcpyHostToDevice, st);
+                        if (e != hipSuccess) return report(TMFWM_ERR_HIP, "tile upload failed");
+                    }
                     if (frame_stride == fbytes)
                         return hipMemcpyAsync(din, rgb + f * frame_stride, (size_t)(k * fbytes), hipMemcpyHostToDevice, st) == hipSuccess
                                    ? 0 : report(TMFWM_ERR_HIP, "frame upload failed");
@@ -489,8 +509,9 @@ int tmfwm_embed_multi_route(const uint8_t *rgb, int64_t n_frames, int32_t height
                             return report(TMFWM_ERR_HIP, "frame upload failed");
                     return 0;
                 },
-                [&](int64_t k, const uint8_t *din, int64_t, uint8_t *dout, hipStream_t st, uint32_t *sink) -> int {
-                    return tmf::embed_device_async(din, k, height, width, fbytes, u.tile, block, alpha, dout, st, sink, route);
+                [&](int64_t k, const uint8_t *din, int64_t half, uint8_t *dout, hipStream_t st, uint32_t *sink) -> int {
+                    return tmf::embed_device_async(din, k, height, width, fbytes, per_frame ? din + half : u.tile,
+                                                   per_frame ? (int64_t)tbytes : 0, block, alpha, dout, st, sink, route);
                 },
                 [&](int64_t f, int64_t k, const uint8_t *dout, hipStream_t st) -> int {
                     if (frame_stride == fbytes)
@@ -501,10 +522,19 @@ int tmfwm_embed_multi_route(const uint8_t *rgb, int64_t n_frames, int32_t height
                             hipSuccess)
                             return report(TMFWM_ERR_HIP, "frame download failed");
                     return 0;
-                });
+                },
+                per_frame ? (int64_t)tbytes : 0);
         });
     }
     return join(sh, th, n_lapack_blocks);
+}
+
+int tmfwm_embed_multi_route(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
+                            const uint8_t *wm_tile, int32_t block, double alpha, uint8_t *out, const int32_t *devices,
+                            int32_t n_shards, int32_t route, int64_t *n_lapack_blocks)
+{
+    return tmfwm_embed_multi_tiles(rgb, n_frames, height, width, frame_stride, wm_tile, 0, block, alpha, out, devices, n_shards, route,
+                                   n_lapack_blocks);
 }
 
 int tmfwm_extract_multi_route(const uint8_t *wm_rgb, const uint8_t *orig_rgb, int64_t n_frames, int32_t height, int32_t width,

@@ -177,7 +177,7 @@ __global__ __launch_bounds__(64, B <= 8 ? 3 : 2) void embed_rank1_kernel(EmbedAr
     for (int j = 0; j < B; ++j) v[j] = v[j] * vinv;
 
     // M_fast = f32(D + c u v^T) (:198 + :201 with the top pair alone)
-    const uint32_t wv = pos.valid ? a.wm[(int64_t)pos.bi * a.nbw + pos.bj] : 0u;
+    const uint32_t wv = pos.valid ? a.wm[pos.frame * a.wm_stride + (int64_t)pos.bi * a.nbw + pos.bj] : 0u;
     const double cw = a.alpha * ((double)wv / 255.0);
 #pragma unroll
     for (int r = 0; r < R; ++r)
@@ -321,6 +321,7 @@ static hipError_t launch_rank1_b(EmbedArgs a, hipStream_t st)
         const int64_t nf = a.nframes - f0 < 65535 ? a.nframes - f0 : 65535;
         c.src = a.src + f0 * a.frame_stride;
         c.dst = a.dst + f0 * a.frame_stride;
+        c.wm = a.wm + f0 * a.wm_stride;
         hipLaunchKernelGGL((embed_rank1_kernel<B>), dim3((unsigned)gx, (unsigned)nf), dim3(64), 0, st, c);
     }
     if (a.slow_list) {  // TMFWM_ROUTE_RANK1: the list pass over the blocks the pre-pass left

@@ -77,13 +77,18 @@ __device__ __forceinline__ uint8_t clip8(int v)
     return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
 }
 
+// The three kernels take the image index from blockIdx.z: image i is read at in + i * istride
+// and written at out + i * ostride (one launch over a batch of equally sized images).
+//
 // out[yy][xx] = clip8(2^21 + sum_x in[yy + y0][xmin + x] * k[xx][x])
-__global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t *__restrict__ in, int iw, int y0, int rows, int ow,
-                                                         const int *__restrict__ bounds, const int *__restrict__ kk, int ks,
-                                                         uint8_t *__restrict__ out, int ldo)
+__global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t *__restrict__ in, int64_t istride, int iw, int y0, int rows,
+                                                         int ow, const int *__restrict__ bounds, const int *__restrict__ kk, int ks,
+                                                         uint8_t *__restrict__ out, int64_t ostride, int ldo)
 {
     const int xx = blockIdx.x * blockDim.x + threadIdx.x, yy = blockIdx.y;
     if (xx >= ow || yy >= rows) return;
+    in += blockIdx.z * istride;
+    out += blockIdx.z * ostride;
     const int xmin = bounds[2 * xx], xmax = bounds[2 * xx + 1];
     const uint8_t *src = in + (int64_t)(yy + y0) * iw + xmin;
     const int *k = kk + (int64_t)xx * ks;
@@ -93,12 +98,14 @@ __global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t *__restri
 }
 
 // out[yy][xx] = clip8(2^21 + sum_y in[ymin + y][xx] * k[yy][y])
-__global__ __launch_bounds__(256) void resample_v_kernel(const uint8_t *__restrict__ in, int iw, int oh,
+__global__ __launch_bounds__(256) void resample_v_kernel(const uint8_t *__restrict__ in, int64_t istride, int iw, int oh,
                                                          const int *__restrict__ bounds, const int *__restrict__ kk, int ks,
-                                                         uint8_t *__restrict__ out, int ldo)
+                                                         uint8_t *__restrict__ out, int64_t ostride, int ldo)
 {
     const int xx = blockIdx.x * blockDim.x + threadIdx.x, yy = blockIdx.y;
     if (xx >= iw || yy >= oh) return;
+    in += blockIdx.z * istride;
+    out += blockIdx.z * ostride;
     const int ymin = bounds[2 * yy], ymax = bounds[2 * yy + 1];
     const int *k = kk + (int64_t)yy * ks;
     int ss = 1 << (kPrecisionBits - 1);
@@ -106,40 +113,63 @@ __global__ __launch_bounds__(256) void resample_v_kernel(const uint8_t *__restri
     out[(int64_t)yy * ldo + xx] = clip8(ss);
 }
 
-__global__ __launch_bounds__(256) void copy_rows_kernel(const uint8_t *__restrict__ in, int iw, int rows,
-                                                        uint8_t *__restrict__ out, int ldo)
+__global__ __launch_bounds__(256) void copy_rows_kernel(const uint8_t *__restrict__ in, int64_t istride, int iw, int rows,
+                                                        uint8_t *__restrict__ out, int64_t ostride, int ldo)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-    if (x < iw && y < rows) out[(int64_t)y * ldo + x] = in[(int64_t)y * iw + x];
+    if (x < iw && y < rows) out[blockIdx.z * ostride + (int64_t)y * ldo + x] = in[blockIdx.z * istride + (int64_t)y * iw + x];
 }
 
-static dim3 grid2(int w, int h) { return dim3((unsigned)((w + 255) / 256), (unsigned)h); }
+static dim3 grid3(int w, int h, int64_t n) { return dim3((unsigned)((w + 255) / 256), (unsigned)h, (unsigned)n); }
 
-// Image.resize((ow, oh), LANCZOS) of in (ih x iw) into out (row stride ldo).
+// Image.resize((ow, oh), LANCZOS) of n images (ih x iw, in_stride bytes apart) into n outputs
+// (row stride ldo, out_stride bytes apart), every pass one launch over a group of at most
+// kResizeGroup images (the grid's z limit is 65535; the group also bounds the scratch).
 // tables: device copy of [bounds_h | kk_h | bounds_v | kk_v] (ResamplePlan::pack),
-// tmp: device scratch of plan.tmp_bytes().
+// tmp: device scratch of resize_tmp_bytes(plan, n).
+hipError_t launch_resize_lanczos_batch(const uint8_t *in, int64_t in_stride, int64_t n, const ResamplePlan &plan, const int *tables,
+                                       uint8_t *tmp, uint8_t *out, int ldo, int64_t out_stride, hipStream_t st)
+{
+    const int ih = plan.ih, iw = plan.iw, oh = plan.oh, ow = plan.ow;
+    const int *bh = tables, *kh = bh + plan.h.bounds.size(), *bv = kh + plan.h.kk.size(), *kv = bv + plan.v.bounds.size();
+    const int64_t tstride = (int64_t)plan.tmp_bytes();
+    for (int64_t i0 = 0; i0 < n; i0 += kResizeGroup) {
+        const int64_t g = n - i0 < kResizeGroup ? n - i0 : kResizeGroup;
+        const uint8_t *gin = in + i0 * in_stride;
+        uint8_t *gout = out + i0 * out_stride;
+        if (oh == ih && ow == iw) {  // Image.resize returns a copy
+            hipLaunchKernelGGL(copy_rows_kernel, grid3(iw, ih, g), dim3(256), 0, st, gin, in_stride, iw, ih, gout, out_stride, ldo);
+            continue;
+        }
+        const uint8_t *src = gin;
+        int64_t sstride = in_stride;
+        int sw = iw;
+        if (plan.need_h) {  // the groups share the scratch: they run in stream order
+            hipLaunchKernelGGL(resample_h_kernel, grid3(ow, plan.rows(), g), dim3(256), 0, st, gin, in_stride, iw, plan.y_first,
+                               plan.rows(), ow, bh, kh, plan.h.ksize, tmp, tstride, ow);
+            src = tmp;
+            sstride = tstride;
+            sw = ow;
+        }
+        if (plan.need_v)
+            hipLaunchKernelGGL(resample_v_kernel, grid3(sw, oh, g), dim3(256), 0, st, src, sstride, sw, oh, bv, kv, plan.v.ksize,
+                               gout, out_stride, ldo);
+        else
+            hipLaunchKernelGGL(copy_rows_kernel, grid3(sw, oh, g), dim3(256), 0, st, src, sstride, sw, oh, gout, out_stride, ldo);
+    }
+    return hipGetLastError();
+}
+
+size_t resize_tmp_bytes(const ResamplePlan &plan, int64_t n)
+{
+    return plan.tmp_bytes() * (size_t)(n < kResizeGroup ? n : kResizeGroup);
+}
+
+// one image: tmp is device scratch of plan.tmp_bytes()
 hipError_t launch_resize_lanczos(const uint8_t *in, const ResamplePlan &plan, const int *tables, uint8_t *tmp, uint8_t *out,
                                  int ldo, hipStream_t st)
 {
-    const int ih = plan.ih, iw = plan.iw, oh = plan.oh, ow = plan.ow;
-    if (oh == ih && ow == iw) {  // Image.resize returns a copy
-        hipLaunchKernelGGL(copy_rows_kernel, grid2(iw, ih), dim3(256), 0, st, in, iw, ih, out, ldo);
-        return hipGetLastError();
-    }
-    const int *bh = tables, *kh = bh + plan.h.bounds.size(), *bv = kh + plan.h.kk.size(), *kv = bv + plan.v.bounds.size();
-    const uint8_t *src = in;
-    int sw = iw;
-    if (plan.need_h) {
-        hipLaunchKernelGGL(resample_h_kernel, grid2(ow, plan.rows()), dim3(256), 0, st, in, iw, plan.y_first, plan.rows(), ow,
-                           bh, kh, plan.h.ksize, tmp, ow);
-        src = tmp;
-        sw = ow;
-    }
-    if (plan.need_v)
-        hipLaunchKernelGGL(resample_v_kernel, grid2(sw, oh), dim3(256), 0, st, src, sw, oh, bv, kv, plan.v.ksize, out, ldo);
-    else
-        hipLaunchKernelGGL(copy_rows_kernel, grid2(sw, oh), dim3(256), 0, st, src, sw, oh, out, ldo);
-    return hipGetLastError();
+    return launch_resize_lanczos_batch(in, 0, 1, plan, tables, tmp, out, ldo, 0, st);
 }
 
 void ResamplePlan::build(int in_h, int in_w, int out_h, int out_w)

@@ -33,21 +33,29 @@ def _device_list(devices):
 def embed_multi(frames: np.ndarray, wm_tile: np.ndarray, block: int = 8, alpha: float = 0.1, devices=None,
                 stats: dict | None = None, route: str = "hybrid") -> np.ndarray:
     """Embed one tile into every frame, frames sharded over `devices` (default: every
-    visible GPU; repeat a device for logical shards).  stats receives "lapack_blocks";
+    visible GPU; repeat a device for logical shards).  wm_tile is (H/b, W/b), shared and
+    broadcast to the devices, or (N, H/b, W/b), one tile per frame: each shard then uploads
+    the tiles of its own frames with them and nothing is broadcast.  stats receives "lapack_blocks";
     route as batch.embed_batch ("hybrid", "reference", "rank1" or "rank1_reference")."""
     frames = _frames(frames, "frames")
     n, h, w, _ = frames.shape
     if block not in SUPPORTED_BLOCK_SIZES:
         raise NotImplementedError(f"block {block}")
     tile = np.ascontiguousarray(wm_tile, dtype=np.uint8)
-    if tile.shape != (h // block, w // block):
-        raise ValueError(f"wm_tile must be ({h // block}, {w // block}), got {tile.shape}")
+    nbh, nbw = h // block, w // block
+    if tile.shape not in ((nbh, nbw), (n, nbh, nbw)):
+        raise ValueError(f"wm_tile must be ({nbh}, {nbw}) or ({n}, {nbh}, {nbw}), got {tile.shape}")
     out = np.empty_like(frames)
     devs, k = _device_list(devices)
     cnt = ctypes.c_int64(0)
     L = _lib.load()
-    _lib.check(L.tmfwm_embed_multi_route(frames.ctypes.data, n, h, w, h * w * 3, tile.ctypes.data, block, float(alpha),
-                                         out.ctypes.data, devs, k, _lib.route_code(route), ctypes.addressof(cnt)), "embed_multi")
+    if tile.ndim == 2:
+        rc = L.tmfwm_embed_multi_route(frames.ctypes.data, n, h, w, h * w * 3, tile.ctypes.data, block, float(alpha),
+                                       out.ctypes.data, devs, k, _lib.route_code(route), ctypes.addressof(cnt))
+    else:
+        rc = L.tmfwm_embed_multi_tiles(frames.ctypes.data, n, h, w, h * w * 3, tile.ctypes.data, nbh * nbw, block, float(alpha),
+                                       out.ctypes.data, devs, k, _lib.route_code(route), ctypes.addressof(cnt))
+    _lib.check(rc, "embed_multi")
     if stats is not None:
         stats["lapack_blocks"] = int(cnt.value)
     return out

@@ -59,7 +59,9 @@ class GpuStage:
     """Device stage: per image, pinned staging + side-stream H2D / embed / D2H.
 
     Returns (pixels, wait) where ``wait()`` blocks until the D2H copy landed.  The
-    tile for an image size is prepared on the device once and reused."""
+    tile for an image size is prepared on the device once and reused.  ``watermark_data``
+    may be a list or tuple of watermarks, one per image: the stage is then called as
+    ``stage(rgb, i)`` and keeps its per-size tile cache per watermark."""
 
     def __init__(self, watermark_data, block: int, alpha: float, preserve_ratio: bool, device=None, route: str = SVD_ROUTE):
         import torch
@@ -70,20 +72,23 @@ class GpuStage:
         self.block, self.alpha, self.preserve_ratio = int(block), float(alpha), bool(preserve_ratio)
         self.route = route  # the drop-in's SVD route (constants.SVD_ROUTE, custom_settings["svd_route"])
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        wm = watermark_data if isinstance(watermark_data, Image.Image) else Image.open(io.BytesIO(watermark_data))
-        grey = np.array(wm.convert("L"), dtype=np.uint8, copy=True)  # watermarking.py:98-103
-        self.wm_grey = torch.from_numpy(grey).to(self.device)
+        self.per_image = isinstance(watermark_data, (list, tuple))
+        self.wm_grey = []  # one grey watermark on the device per watermark
+        for data in (watermark_data if self.per_image else [watermark_data]):
+            wm = data if isinstance(data, Image.Image) else Image.open(io.BytesIO(data))
+            grey = np.array(wm.convert("L"), dtype=np.uint8, copy=True)  # watermarking.py:98-103
+            self.wm_grey.append(torch.from_numpy(grey).to(self.device))
         self.stream = torch.cuda.Stream(device=self.device)
-        self.tiles: dict[tuple[int, int], object] = {}
+        self.tiles: dict[tuple[int, int, int], object] = {}  # (watermark, nbh, nbw) -> tile
 
-    def _tile(self, nbh: int, nbw: int):
-        key = (nbh, nbw)
+    def _tile(self, nbh: int, nbw: int, index: int = 0):
+        key = (index, nbh, nbw)
         if key not in self.tiles:
             with self.torch.cuda.stream(self.stream):
-                self.tiles[key] = self.batch.prepare_tile(self.wm_grey, nbh, nbw, self.preserve_ratio, stream=self.stream)
+                self.tiles[key] = self.batch.prepare_tile(self.wm_grey[index], nbh, nbw, self.preserve_ratio, stream=self.stream)
         return self.tiles[key]
 
-    def __call__(self, rgb: np.ndarray):
+    def __call__(self, rgb: np.ndarray, index: int = 0):
         torch = self.torch
         h, w = rgb.shape[:2]
         nbh, nbw = h // self.block, w // self.block
@@ -92,7 +97,7 @@ class GpuStage:
         host_in = torch.empty((1, h, w, 3), dtype=torch.uint8, pin_memory=True)
         host_in.numpy()[0] = rgb
         host_out = torch.empty((1, h, w, 3), dtype=torch.uint8, pin_memory=True)
-        tile = self._tile(nbh, nbw)
+        tile = self._tile(nbh, nbw, index)
         with torch.cuda.stream(self.stream):
             dev_in = host_in.to(self.device, non_blocking=True)
             dev_out = self.batch.embed_batch(dev_in, tile, self.block, self.alpha, stream=self.stream, route=self.route)
@@ -112,18 +117,26 @@ def embed_images(images: Iterable, watermark_data, preserve_ratio: bool = True, 
                  workers: int | None = None, device_stage: Callable | None = None) -> list[Embedded]:
     """Embed ``watermark_data`` (PNG bytes or PIL image) into every image (bytes, file
     object or PIL image) -- embed_watermark_page.py:492-558 without the per-image
-    serialisation.  Returns, in input order, the watermarked pixels and PNG bytes."""
+    serialisation.  Returns, in input order, the watermarked pixels and PNG bytes.
+
+    ``watermark_data`` may also be a list or tuple with one watermark per image (a service
+    watermarking many users' images: no two QR codes are alike): image i gets watermark i, a
+    length mismatch raises ValueError, and a custom ``device_stage`` is called as
+    ``stage(rgb, i)`` instead of ``stage(rgb)``."""
     settings = custom_settings or {}
     block = int(settings.get("block_size", BLOCK_SIZE))
     alpha = float(settings.get("alpha", ALPHA))
     route = settings.get("svd_route") or os.environ.get("TMFWM_SVD_ROUTE") or SVD_ROUTE  # as watermarking._route
+    sources: Sequence = list(images)
+    per_image = isinstance(watermark_data, (list, tuple))
+    if per_image and len(watermark_data) != len(sources):
+        raise ValueError(f"{len(watermark_data)} watermarks for {len(sources)} images")
     stage = device_stage or GpuStage(watermark_data, block, alpha, preserve_ratio, route=route)
     n_workers = workers or min(16, max(2, (len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 4)))
-    sources: Sequence = list(images)
     with ThreadPoolExecutor(n_workers, thread_name_prefix="tmf-io") as pool:
         decoded: list[Future] = [pool.submit(_decode, s) for s in sources]
         encoded: list[Future] = []
-        for fut in decoded:  # the device stage runs in order on this thread
-            pixels, wait = stage(fut.result())
+        for i, fut in enumerate(decoded):  # the device stage runs in order on this thread
+            pixels, wait = stage(fut.result(), i) if per_image else stage(fut.result())
             encoded.append(pool.submit(_encode, pixels, wait))
         return [f.result() for f in encoded]
