@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "tmfwm_device.h"
+#include "tmfwm_colour_tail.h"
 #include "tmfwm_internal.h"
 
 namespace tmf {
@@ -292,6 +293,16 @@ constexpr bool kOffsetPick = B == 8 || B == 16;
 template <int B>
 constexpr bool kReloadBytes = B == 16;
 
+// The colour tail decides its bytes in f32 and redoes the undecided pixels in f64
+// (tmfwm_colour_tail.h); false keeps the exact f64 tail alone.  The kernels that would spill more
+// with both tails keep it: b = 12 (60 VGPRs spilled against 59, scratch 192 bytes against 184) and
+// the list passes of b = 8, 10, 14 (7 / 8 / 73 against 3 / 6 / 71), which run ~1 % of the blocks.
+#ifndef TMF_FAST_TAIL
+#define TMF_FAST_TAIL true
+#endif
+template <int B, bool LIST>
+constexpr bool kFastTail = TMF_FAST_TAIL && B != 12 && !(LIST && (B == 8 || B == 10 || B == 14));
+
 // b = 10 / 14 keep the reconstruction's fma chains in their (k-outer) source order: left free,
 // the compiler regroups them per output element and spills every element of Bm it reads
 // ahead of its use (272 / 282 VGPRs spilled -> 0 / 5; embed<14> 613 -> 360 us per 4K frame,
@@ -553,35 +564,26 @@ TMF_DEVI void embed_blocks(const EmbedArgs &a, const StripPos &pos, uint32_t id,
     bool unc = neg;
     if (pos.valid && !slow) {
         if constexpr (kReloadBytes<B>) load_block_rows<B>(src, a.W, pos, q, a.aligned, words);
+        bool hot = false;  // wave-uniform: the rows that follow skip the f32 decision (tmfwm_colour_tail.h)
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             uint32_t out[Geo<B>::NW];
+            if constexpr (kFastTail<B, LIST>) {
+                // the f32 decision over the row, the exact f64 tail where it rejects (tmfwm_colour_tail.h)
+                colour_tail_row<B>(words[r], [&](int c) { return TailY{Ml[r][c], Mh[r][c], Mh[r][c] - Ml[r][c]}; }, out, unc, hot);
+            } else {
 #pragma unroll
-            for (int i = 0; i < Geo<B>::NW; ++i) out[i] = 0u;
+                for (int i = 0; i < Geo<B>::NW; ++i) out[i] = 0u;
 #pragma unroll
-            for (int c = 0; c < B; ++c) {
-                float cbs, crs;
-                const uint32_t R0 = byte_at(words[r], 3 * c), G0 = byte_at(words[r], 3 * c + 1), B0 = byte_at(words[r], 3 * c + 2);
-                chroma(R0, G0, B0, cbs, crs);
-                uint32_t R8, G8, B8;
-                float fr;
-                colour_inv_frac(Ml[r][c], cbs, crs, R8, G8, B8, fr);
-                // Every channel is monotone in Y, and from Y's lower end to its upper end each
-                // scaled value p = f32(clip(v) * 255) grows by at most 255 dY + 255 * 2^-24 +
-                // 2^-16 (v's f32 rounding on [0, 1], then p's) < 255.1 dY + 2^-14, dY = f32(Yh -
-                // Yl); so the bytes cannot differ unless frac(p) + that reaches 1, and only then
-                // are the upper end's bytes computed
-                const float dy = Mh[r][c] - Ml[r][c];
-                const bool wide = dy != 0.0f && fr + __builtin_fmaf(dy, 255.1f, 0x1p-14f) >= 1.0f;
-                if (__builtin_amdgcn_ballot_w64(wide) != 0 && wide) {
-                    uint32_t R9, G9, B9;
-                    colour_inv(Mh[r][c], cbs, crs, R9, G9, B9);
-                    unc = unc || R9 != R8 || G9 != G8 || B9 != B8;
+                for (int c = 0; c < B; ++c) {
+                    const uint32_t R0 = byte_at(words[r], 3 * c), G0 = byte_at(words[r], 3 * c + 1), B0 = byte_at(words[r], 3 * c + 2);
+                    uint32_t R8, G8, B8;
+                    colour_tail_exact(R0, G0, B0, Ml[r][c], Mh[r][c], Mh[r][c] - Ml[r][c], R8, G8, B8, unc);
+                    const int k0 = 3 * c;
+                    out[k0 >> 2] |= R8 << (8 * (k0 & 3));
+                    out[(k0 + 1) >> 2] |= G8 << (8 * ((k0 + 1) & 3));
+                    out[(k0 + 2) >> 2] |= B8 << (8 * ((k0 + 2) & 3));
                 }
-                const int k0 = 3 * c;
-                out[k0 >> 2] |= R8 << (8 * (k0 & 3));
-                out[(k0 + 1) >> 2] |= G8 << (8 * ((k0 + 1) & 3));
-                out[(k0 + 2) >> 2] |= B8 << (8 * ((k0 + 2) & 3));
             }
             uint8_t *p = dst + ((int64_t)(pos.bi * B + q * R + r) * a.W + (int64_t)pos.bj * B) * 3;
             if (real_row<B>(q, r)) store_words<B>(p, a.aligned, out);

@@ -231,7 +231,7 @@ __global__ __launch_bounds__(64, B <= 8 ? 3 : 2) void embed_rank1_kernel(EmbedAr
     dct2d_rows_layout<B, true>(x, tile, q);  // :204, Y_fast
 
     // :207-216 at both ends of [Y_fast - eps_Y, Y_fast + eps_Y]
-    bool unc = false;
+    bool unc = false, hot = false;  // hot: tmfwm_colour_tail.h
     uint32_t outw[R][NW];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -256,12 +256,9 @@ __global__ __launch_bounds__(64, B <= 8 ? 3 : 2) void embed_rank1_kernel(EmbedAr
         });
         uint32_t words[NW];
 #pragma unroll
-        for (int i = 0; i < NW; ++i) {
-            outw[r][i] = 0u;
-            words[i] = pix[r * NW + i][lane];
-        }
-#pragma unroll
-        for (int c = 0; c < B; ++c) {
+        for (int i = 0; i < NW; ++i) words[i] = pix[r * NW + i][lane];
+        // Y's interval of pixel c of this row: [Y_fast - eps_Y, Y_fast + eps_Y]
+        const auto yint = [&](int c) {
             const float y = x[r][c];
             // the ones term's column factors are compile-time sums of the tables
             float B3 = 0.0f, EB3 = 0.0f;
@@ -273,24 +270,9 @@ __global__ __launch_bounds__(64, B <= 8 ? 3 : 2) void embed_rank1_kernel(EmbedAr
             const float t3 = Sp * __builtin_fmaf(2.0f * u24, EB3, B3) + ESp * (2.0f * u24) * __builtin_fmaf(u24, EB3, B3);
             const float ey = (Ap * P1[c] + EAp * Q1[c] + Up * P2[c] + EUp * Q2[c] + ga * t3) * (1.0f + 0x1p-16f) +
                              __builtin_fabsf(y) * 0x1p-22f + 0x1p-40f;
-            float cbs, crs;
-            const uint32_t R0 = byte_at(words, 3 * c), G0 = byte_at(words, 3 * c + 1), B0 = byte_at(words, 3 * c + 2);
-            chroma(R0, G0, B0, cbs, crs);
-            uint32_t R8, G8, B8;
-            float fr;
-            colour_inv_frac(y - ey, cbs, crs, R8, G8, B8, fr);
-            const float dy = 2.0f * ey;
-            const bool wide = fr + __builtin_fmaf(dy, 255.1f, 0x1p-14f) >= 1.0f;
-            if (__builtin_amdgcn_ballot_w64(wide) != 0 && wide) {
-                uint32_t R9, G9, B9;
-                colour_inv(y + ey, cbs, crs, R9, G9, B9);
-                unc = unc || R9 != R8 || G9 != G8 || B9 != B8;
-            }
-            const int k0 = 3 * c;
-            outw[r][k0 >> 2] |= R8 << (8 * (k0 & 3));
-            outw[r][(k0 + 1) >> 2] |= G8 << (8 * ((k0 + 1) & 3));
-            outw[r][(k0 + 2) >> 2] |= B8 << (8 * ((k0 + 2) & 3));
-        }
+            return TailY{y - ey, y + ey, 2.0f * ey};
+        };
+        colour_tail_row<B>(words, yint, outw[r], unc, hot);
     }
     ok = ok && group_or<L>(unc ? 1 : 0) == 0;
     if (!pos.valid) return;
