@@ -193,6 +193,56 @@ int tmfwm_embed_tiles(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_fra
                       int32_t out_pixel_bytes, int64_t out_frame_stride, int32_t mem_kind, void *hip_stream, int32_t route,
                       int64_t *n_lapack_blocks);
 
+/*
+ * Ragged batches (added within ABI 10; the version number is unchanged and existing entry points
+ * keep their behaviour): n_frames frames of mixed sizes, each with its own buffers and its own
+ * tile, embedded or extracted by one set of launches.  Every frame's bytes are exactly what
+ * tmfwm_embed_route / tmfwm_extract_route give for that frame alone.
+ *
+ * One descriptor per frame.  The descriptor array itself is always host memory, whatever
+ * mem_kind says about the pointers inside it; the library copies it before it returns, so the
+ * caller may free or reuse it at once (also after an asynchronous TMFWM_MEM_DEVICE call).
+ * Pixels are 3 bytes (TMFWM_PIX_RGB), rows packed: height x width x 3 bytes per image; the tile
+ * is (height/block) x (width/block) bytes, packed.  A frame with height < block or
+ * width < block has no block: embed writes its colour round trip, extract writes nothing for
+ * it.  A frame with height == 0 or width == 0 is skipped (its pointers are not looked at).
+ */
+typedef struct {
+    const uint8_t *rgb;      /* height x width x 3, packed rows */
+    uint8_t *out;            /* same shape */
+    const uint8_t *wm_tile;  /* (height/block) x (width/block), packed */
+    int32_t height, width;
+} tmfwm_embed_frame;
+
+typedef struct {
+    const uint8_t *wm_rgb, *orig_rgb;  /* both height x width x 3 */
+    uint8_t *out_tile;                 /* (height/block) x (width/block) */
+    int32_t height, width;
+} tmfwm_extract_frame;
+
+/*
+ * Embed a ragged batch.  TMFWM_MEM_HOST: the frames are staged into one device allocation, the
+ * results copied back, and the call returns when they have landed (tmfwm_embed's contract).
+ * TMFWM_MEM_DEVICE: asynchronous on `hip_stream` unless n_lapack_blocks is given; every `out`
+ * must be disjoint from every `rgb` and `wm_tile` of the call and from every other `out`
+ * (TMFWM_ERR_INVALID otherwise; inputs may share memory).  Routes: TMFWM_ROUTE_HYBRID and
+ * TMFWM_ROUTE_REFERENCE; the ragged calls do not take the rank-1 routes yet
+ * (TMFWM_ROUTE_RANK1 and TMFWM_ROUTE_RANK1_REFERENCE return TMFWM_ERR_UNSUPPORTED).
+ * *n_lapack_blocks (optional) receives the dgesdd-route blocks of all frames together; a dbdsqr
+ * that does not converge fails a synchronising call as it does tmfwm_embed_ex.  The strip pass
+ * runs every block to the end (no list pass): tmfwm_last_list_pass_blocks() reports 0.
+ * All arguments are checked before the device is touched.
+ */
+int tmfwm_embed_ragged(const tmfwm_embed_frame *frames, int64_t n_frames, int32_t block, double alpha, int32_t mem_kind,
+                       void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
+
+/* Extract a ragged batch: frame i's tile from its watermarked and original image (one size per
+ * pair).  Memory kinds, routes, the count and the checks as tmfwm_embed_ragged; every `out_tile`
+ * must be disjoint from the call's inputs and from every other `out_tile`; alpha must be finite
+ * and non-zero. */
+int tmfwm_extract_ragged(const tmfwm_extract_frame *frames, int64_t n_frames, int32_t block, double alpha, int32_t mem_kind,
+                         void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
+
 /* tmfwm_extract_route with a pixel layout and frame stride per input image (ABI 8). */
 int tmfwm_extract_px(const uint8_t *wm_rgb, int32_t wm_pixel_bytes, int64_t wm_frame_stride, const uint8_t *orig_rgb,
                      int32_t orig_pixel_bytes, int64_t orig_frame_stride, int64_t n_frames, int32_t height, int32_t width,

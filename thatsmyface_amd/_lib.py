@@ -58,6 +58,22 @@ _I32 = ctypes.c_int32
 _D = ctypes.c_double
 _VP = ctypes.c_void_p
 
+
+
+class EmbedFrame(ctypes.Structure):
+    """tmfwm_embed_frame: one frame of tmfwm_embed_ragged (include/tmfwm.h)."""
+
+    _fields_ = [("rgb", ctypes.c_void_p), ("out", ctypes.c_void_p), ("wm_tile", ctypes.c_void_p),
+                ("height", ctypes.c_int32), ("width", ctypes.c_int32)]
+
+
+class ExtractFrame(ctypes.Structure):
+    """tmfwm_extract_frame: one frame pair of tmfwm_extract_ragged (include/tmfwm.h)."""
+
+    _fields_ = [("wm_rgb", ctypes.c_void_p), ("orig_rgb", ctypes.c_void_p), ("out_tile", ctypes.c_void_p),
+                ("height", ctypes.c_int32), ("width", ctypes.c_int32)]
+
+
 # name -> (restype, argtypes): exactly the entry points of include/tmfwm.h
 SIGNATURES = {
     "tmfwm_abi_version": (ctypes.c_int, []),
@@ -73,6 +89,8 @@ SIGNATURES = {
     "tmfwm_extract_route": (ctypes.c_int, [_VP, _VP, _I64, _I32, _I32, _I64, _I32, _D, _VP, _I32, _VP, _I32, _VP]),
     "tmfwm_embed_px": (ctypes.c_int, [_VP, _I32, _I64, _I64, _I32, _I32, _VP, _I32, _D, _VP, _I32, _I64, _I32, _VP, _I32, _VP]),
     "tmfwm_embed_tiles": (ctypes.c_int, [_VP, _I32, _I64, _I64, _I32, _I32, _VP, _I64, _I32, _D, _VP, _I32, _I64, _I32, _VP, _I32, _VP]),
+    "tmfwm_embed_ragged": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _VP, _I32, _VP]),
+    "tmfwm_extract_ragged": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _VP, _I32, _VP]),
     "tmfwm_extract_px": (ctypes.c_int, [_VP, _I32, _I64, _VP, _I32, _I64, _I64, _I32, _I32, _I32, _D, _VP, _I32, _VP, _I32, _VP]),
     "tmfwm_embed_multi": (ctypes.c_int, [_VP, _I64, _I32, _I32, _I64, _VP, _I32, _D, _VP, _VP, _I32, _VP]),
     "tmfwm_release_cached_buffers": (ctypes.c_int, []),

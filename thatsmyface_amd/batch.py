@@ -111,6 +111,127 @@ def extract_batch(wframes: torch.Tensor, oframes: torch.Tensor, block: int = 8, 
     return out
 
 
+def _check_ragged(frames, name: str, device=None):
+    """A sequence of (H_i, W_i, 3) uint8 contiguous GPU tensors on one device -> (list, device)."""
+    frames = list(frames)
+    for i, t in enumerate(frames):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{name}[{i}] must be a GPU tensor")
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[-1] != 3:
+            raise ValueError(f"{name}[{i}] must be (H, W, 3) uint8, got {tuple(t.shape)} {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}[{i}] must be contiguous")
+        device = t.device if device is None else device
+        if t.device != device:
+            raise ValueError(f"{name}[{i}] is on {t.device}, the call's other tensors on {device}")
+    return frames, device
+
+
+def _ragged_views(sizes, shape_of, device) -> list:
+    """One uint8 device allocation cut into per-frame views (each 16-byte aligned)."""
+    offs, total = [], 0
+    for s in sizes:
+        offs.append(total)
+        total += (s + 15) & ~15
+    buf = torch.empty((total,), dtype=torch.uint8, device=device)
+    return [buf[o:o + s].view(shape_of(i)) for i, (o, s) in enumerate(zip(offs, sizes))]
+
+
+def _ragged_route(route) -> int:
+    code = _lib.route_code(route)
+    if code in (_lib.ROUTE_RANK1, _lib.ROUTE_RANK1_REFERENCE):
+        raise NotImplementedError("the ragged calls do not take the rank-1 routes yet")
+    return code
+
+
+def embed_ragged(frames, tiles, block: int = 8, alpha: float = 0.1, out=None, stream=None, stats: dict | None = None,
+                 route: str = "hybrid") -> list:
+    """Embed frames of mixed sizes, each with its own tile, by one set of launches
+    (tmfwm_embed_ragged): frames[i] is (H_i, W_i, 3) uint8, tiles[i] (H_i // block, W_i // block)
+    uint8, all contiguous on one GPU.  Returns the outputs as per-frame views of one device
+    allocation (or `out`, a sequence of tensors shaped like the frames); output i is the bytes
+    of embed_batch(frames[i][None], tiles[i], ...)[0].  A frame smaller than a block gets its
+    colour round trip.  stats and route ("hybrid" / "reference") as embed_batch's; no list pass
+    runs, so "list_pass_blocks" is 0."""
+    import ctypes
+
+    if block not in SUPPORTED_BLOCK_SIZES:
+        raise NotImplementedError(f"block {block}")
+    code = _ragged_route(route)
+    frames, dev = _check_ragged(frames, "frames")
+    tiles = list(tiles)
+    if len(tiles) != len(frames):
+        raise ValueError(f"{len(tiles)} tiles for {len(frames)} frames")
+    for i, (f, t) in enumerate(zip(frames, tiles)):
+        want = (f.shape[0] // block, f.shape[1] // block)
+        if (not isinstance(t, torch.Tensor) or tuple(t.shape) != want or t.dtype != torch.uint8 or t.device != dev
+                or not t.is_contiguous()):
+            raise ValueError(f"tiles[{i}] must be a contiguous {want} uint8 tensor on {dev}")
+    if out is None:
+        out = _ragged_views([f.numel() for f in frames], lambda i: frames[i].shape, dev) if frames else []
+    else:
+        out, _ = _check_ragged(out, "out", dev)
+        if len(out) != len(frames) or any(o.shape != f.shape for o, f in zip(out, frames)):
+            raise ValueError("out must hold one tensor per frame, shaped like it")
+    desc = (_lib.EmbedFrame * max(len(frames), 1))()
+    for i, (f, t, o) in enumerate(zip(frames, tiles, out)):
+        desc[i] = _lib.EmbedFrame(f.data_ptr(), o.data_ptr(), t.data_ptr(), f.shape[0], f.shape[1])
+    cnt, ptr = _count_ptr(stats)
+    L = _lib.load()
+    if frames:
+        with torch.cuda.device(dev):
+            _lib.check(L.tmfwm_embed_ragged(ctypes.addressof(desc), len(frames), block, float(alpha), _lib.MEM_DEVICE,
+                                            _stream(stream), code, ptr), "embed_ragged")
+    if stats is not None:
+        stats["lapack_blocks"] = int(cnt.value)
+        stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks()) if frames else 0
+    return list(out)
+
+
+def extract_ragged(wframes, oframes, block: int = 8, alpha: float = 0.1, out=None, stream=None, stats: dict | None = None,
+                   route: str = "hybrid") -> list:
+    """Extract the tiles of frame pairs of mixed sizes by one set of launches
+    (tmfwm_extract_ragged): wframes[i] and oframes[i] are (H_i, W_i, 3) uint8 of one shape.
+    Returns per-frame (H_i // block, W_i // block) tiles, views of one device allocation (or
+    `out`); tile i is the bytes of extract_batch(wframes[i][None], oframes[i][None], ...)[0]."""
+    import ctypes
+
+    if block not in SUPPORTED_BLOCK_SIZES:
+        raise NotImplementedError(f"block {block}")
+    code = _ragged_route(route)
+    wframes, dev = _check_ragged(wframes, "wframes")
+    oframes, _ = _check_ragged(oframes, "oframes", dev)
+    if len(wframes) != len(oframes):
+        raise ValueError(f"{len(wframes)} watermarked frames for {len(oframes)} originals")
+    for i, (w, o) in enumerate(zip(wframes, oframes)):
+        if w.shape != o.shape:
+            raise ValueError(f"wframes[{i}] / oframes[{i}] shapes differ")
+    shapes = [(w.shape[0] // block, w.shape[1] // block) for w in wframes]
+    if out is None:
+        out = _ragged_views([a * b for a, b in shapes], lambda i: shapes[i], dev) if wframes else []
+    else:
+        out = list(out)
+        if len(out) != len(wframes):
+            raise ValueError("out must hold one tile per frame")
+        for i, t in enumerate(out):
+            if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shapes[i] or t.dtype != torch.uint8 or t.device != dev
+                    or not t.is_contiguous()):
+                raise ValueError(f"out[{i}] must be a contiguous {shapes[i]} uint8 tensor on {dev}")
+    desc = (_lib.ExtractFrame * max(len(wframes), 1))()
+    for i, (w, o, t) in enumerate(zip(wframes, oframes, out)):
+        desc[i] = _lib.ExtractFrame(w.data_ptr(), o.data_ptr(), t.data_ptr(), w.shape[0], w.shape[1])
+    cnt, ptr = _count_ptr(stats)
+    L = _lib.load()
+    if wframes:
+        with torch.cuda.device(dev):
+            _lib.check(L.tmfwm_extract_ragged(ctypes.addressof(desc), len(wframes), block, float(alpha), _lib.MEM_DEVICE,
+                                              _stream(stream), code, ptr), "extract_ragged")
+    if stats is not None:
+        stats["lapack_blocks"] = int(cnt.value)
+        stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks()) if wframes else 0
+    return list(out)
+
+
 def synth_frames(n: int, height: int, width: int, seed: int = SEED_COVER, frame0: int = 0,
                  device: torch.device | str | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
     """Counter-based synthetic uint8 frames generated directly in HBM."""

@@ -15,6 +15,7 @@
 
 #include "../../include/tmfwm.h"
 #include "tmfwm_internal.h"
+#include "tmfwm_ragged.h"
 
 namespace {
 
@@ -1193,6 +1194,342 @@ int tmfwm_prepare_tile(const uint8_t *wm, int32_t wm_height, int32_t wm_width, i
     // the batched call with one watermark (the size check comes before the stride checks)
     return tmfwm_prepare_tiles(wm, 1, wm_height, wm_width, (int64_t)wm_height * wm_width, tile_height, tile_width, preserve_ratio,
                                tile, (int64_t)tile_height * tile_width, mem_kind, hip_stream);
+}
+
+// ---- ragged batches (tmfwm_ragged.h): frames of mixed sizes through one set of launches
+extern "C++" {
+namespace {
+
+// One frame of a ragged call once its descriptor is checked (embed: in0 = rgb, in1 = wm_tile;
+// extract: in0 = wm_rgb, in1 = orig_rgb); the descriptor array is not read after that.
+struct RFrame {
+    const uint8_t *in0, *in1;
+    uint8_t *out;
+    int32_t H, W;
+    int64_t pixel_bytes() const { return (int64_t)H * W * 3; }
+    int64_t tile_bytes(int b) const { return (int64_t)(H / b) * (W / b); }
+};
+
+// the checks every ragged call makes before it touches the device
+int check_ragged_call(const void *frames, int64_t n, int32_t block, double alpha, bool extract, int32_t mem_kind, int32_t route,
+                      int64_t *n_lapack)
+{
+    if (route < TMFWM_ROUTE_HYBRID || route > TMFWM_ROUTE_RANK1_REFERENCE) return fail(TMFWM_ERR_INVALID, "route %d", route);
+    if (route == TMFWM_ROUTE_RANK1 || route == TMFWM_ROUTE_RANK1_REFERENCE)
+        return fail(TMFWM_ERR_UNSUPPORTED, "the ragged calls do not take the rank-1 routes yet (route %d)", route);
+    if (n_lapack) {
+        *n_lapack = 0;
+        t_list_pass = 0;  // no list pass in a ragged call
+    }
+    if (n < 0) return fail(TMFWM_ERR_INVALID, "negative size (n=%lld)", (long long)n);
+    if (n > 0 && !frames) return fail(TMFWM_ERR_INVALID, "frames is NULL");
+    if (!supported_block(block)) return fail(TMFWM_ERR_UNSUPPORTED, "block size %d not supported (even, 4..16)", block);
+    if (mem_kind != TMFWM_MEM_HOST && mem_kind != TMFWM_MEM_DEVICE) return fail(TMFWM_ERR_INVALID, "mem_kind %d", mem_kind);
+    if (extract ? (!std::isfinite(alpha) || alpha == 0.0) : !std::isfinite(alpha))
+        return fail(TMFWM_ERR_INVALID, extract ? "alpha must be finite and non-zero" : "alpha is not finite");
+    return 0;
+}
+
+// one frame's sizes and pointers (the tile pointer only where the frame has a block)
+int check_ragged_frame(int64_t i, const RFrame &f, int32_t block, bool extract)
+{
+    if (int rc = check_frames(1, f.H, f.W, f.pixel_bytes(), block)) return fail(rc, "frame %lld: %s", (long long)i, t_err.c_str());
+    if (f.H == 0 || f.W == 0) return 0;
+    if (f.tile_bytes(block) > 0x7FFFFFFFll) return fail(TMFWM_ERR_INVALID, "frame %lld: more than 2^31 - 1 blocks", (long long)i);
+    const bool tile = f.tile_bytes(block) > 0;
+    if (extract ? (tile && (!f.in0 || !f.in1 || !f.out)) : (!f.in0 || !f.out || (tile && !f.in1)))
+        return fail(TMFWM_ERR_INVALID, "frame %lld: NULL pointer in the descriptor", (long long)i);
+    return 0;
+}
+
+// No output of the call may share a byte with an input or with another output: the intervals
+// sorted by start, one sweep that keeps the furthest end of the inputs and of the outputs so far.
+struct Span {
+    uintptr_t lo, hi;
+    bool out;
+    int64_t frame;
+};
+
+int check_ragged_overlap(std::vector<Span> &spans)
+{
+    std::sort(spans.begin(), spans.end(), [](const Span &a, const Span &b) { return a.lo < b.lo; });
+    uintptr_t in_hi = 0, out_hi = 0;
+    int64_t in_f = -1, out_f = -1;
+    for (const Span &s : spans) {
+        if (s.lo == s.hi) continue;
+        if (s.out && s.lo < in_hi) return fail(TMFWM_ERR_INVALID, "frame %lld's output overlaps an input of frame %lld", (long long)s.frame, (long long)in_f);
+        if (s.out && s.lo < out_hi) return fail(TMFWM_ERR_INVALID, "frame %lld's output overlaps frame %lld's", (long long)s.frame, (long long)out_f);
+        if (!s.out && s.lo < out_hi) return fail(TMFWM_ERR_INVALID, "frame %lld's output overlaps an input of frame %lld", (long long)out_f, (long long)s.frame);
+        if (s.out && s.hi > out_hi) out_hi = s.hi, out_f = s.frame;
+        if (!s.out && s.hi > in_hi) in_hi = s.hi, in_f = s.frame;
+    }
+    return 0;
+}
+
+int check_ragged_device(const std::vector<RFrame> &fr, int32_t block, bool extract)
+{
+    std::vector<Span> spans;
+    spans.reserve(fr.size() * 3);
+    auto add = [&](const void *p, int64_t bytes, bool out, int64_t i) {
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
+        spans.push_back({lo, lo + (uintptr_t)bytes, out, i});
+    };
+    for (size_t i = 0; i < fr.size(); ++i) {
+        const RFrame &f = fr[i];
+        const int64_t px = f.pixel_bytes(), tb = f.tile_bytes(block);
+        if (px == 0 || (extract && tb == 0)) continue;
+        if (int rc = check_device_ptr(f.in0, extract ? "wm_rgb" : "rgb")) return rc;
+        if (extract || tb)
+            if (int rc = check_device_ptr(f.in1, extract ? "orig_rgb" : "wm_tile")) return rc;
+        if (int rc = check_device_ptr(f.out, extract ? "out_tile" : "out")) return rc;
+        add(f.in0, px, false, (int64_t)i);
+        add(f.in1, extract ? px : tb, false, (int64_t)i);
+        add(f.out, extract ? tb : px, true, (int64_t)i);
+    }
+    return check_ragged_overlap(spans);
+}
+
+// Pinned host buffers for the frame table of an asynchronous call: the table is built in one,
+// copied to the device on the call's stream, and the buffer goes back to the free list with an
+// event recorded behind the copy; whoever takes it next waits for that event first.
+struct TableSlot {
+    void *p = nullptr;
+    size_t cap = 0;
+    int dev = 0;
+    hipEvent_t ev = nullptr;
+};
+std::mutex g_table_mu;
+std::vector<TableSlot> g_tables;
+constexpr size_t kTableSlots = 8;
+
+void drop_table(TableSlot &s)
+{
+    if (s.ev) {
+        (void)hipEventSynchronize(s.ev);
+        (void)hipEventDestroy(s.ev);
+    }
+    if (s.p) (void)hipHostFree(s.p);
+    (void)hipGetLastError();
+    s = TableSlot{};
+}
+
+int take_table(size_t bytes, int dev, TableSlot &s)
+{
+    {
+        std::lock_guard<std::mutex> g(g_table_mu);
+        for (size_t i = 0; i < g_tables.size(); ++i)
+            if (g_tables[i].dev == dev && g_tables[i].cap >= bytes) {
+                s = g_tables[i];
+                g_tables.erase(g_tables.begin() + (long)i);
+                break;
+            }
+    }
+    if (s.p) {
+        TMF_HIP(hipEventSynchronize(s.ev));  // the last copy out of it is done
+        return 0;
+    }
+    s.dev = dev;
+    s.cap = bytes < 16384 ? 16384 : bytes;
+    if (hipHostMalloc(&s.p, s.cap, hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&s.ev, hipEventDisableTiming) != hipSuccess) {
+        drop_table(s);
+        return fail(TMFWM_ERR_NOMEM, "pinned allocation of %zu bytes for the frame table failed", bytes);
+    }
+    return 0;
+}
+
+void give_table(TableSlot &s, hipStream_t st)
+{
+    if (!s.p) return;
+    if (hipEventRecord(s.ev, st) != hipSuccess) {  // cannot tell when the copy ends: wait for it
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(st);
+    }
+    std::lock_guard<std::mutex> g(g_table_mu);
+    if (g_tables.size() < kTableSlots) g_tables.push_back(s);
+    else drop_table(s);
+    s = TableSlot{};
+}
+
+// Chunks of whole frames: at most list_cap() blocks each (block ids are 32-bit and relative to
+// the chunk; a frame that alone has more is a chunk of its own, as Chunks::plan has it) and few
+// enough edge pixels for one launch of the edge pass.
+struct RaggedChunk {
+    int64_t first = 0, n = 0, waves = 0, blocks = 0, edge = 0;
+};
+constexpr int64_t kEdgeCap = int64_t(1) << 38;
+
+// the frame table of the frames that have work, with chunk-relative prefixes, and the chunks
+void plan_ragged(const std::vector<RFrame> &fr, int32_t block, bool extract, std::vector<tmf::RaggedFrame> &table,
+                 std::vector<RaggedChunk> &chunks)
+{
+    const int bpw = tmf::ragged_strip_blocks(block);
+    const int64_t cap = list_cap();
+    RaggedChunk c;
+    for (const RFrame &f : fr) {
+        tmf::RaggedFrame t{};
+        t.in0 = f.in0;
+        t.in1 = f.in1;
+        t.out = f.out;
+        t.H = f.H;
+        t.W = f.W;
+        t.nbh = f.H / block;
+        t.nbw = f.W / block;
+        t.strips_per_row = (t.nbw + bpw - 1) / bpw;
+        t.aligned = tmf::dev_aligned(f.in0, extract ? f.in1 : f.out, 0, f.W);
+        const int64_t waves = (int64_t)t.nbh * t.strips_per_row, blocks = (int64_t)t.nbh * t.nbw;
+        const int64_t edge = extract ? 0 : (int64_t)f.H * f.W - blocks * block * block;
+        if (blocks == 0 && edge == 0) continue;
+        if (c.n > 0 && (c.blocks + blocks > cap || c.edge + edge > kEdgeCap)) {
+            chunks.push_back(c);
+            c = RaggedChunk{};
+            c.first = (int64_t)table.size();
+        }
+        t.wave0 = (uint32_t)c.waves;
+        t.block0 = (uint32_t)c.blocks;
+        t.edge0 = c.edge;
+        table.push_back(t);
+        ++c.n;
+        c.waves += waves;
+        c.blocks += blocks;
+        c.edge += edge;
+    }
+    if (c.n > 0) chunks.push_back(c);
+}
+
+// Both passes of a ragged call over device-resident frames; counts as run_embed / run_extract
+// (read back when the caller asks for the count or `check` is set; `sink` takes them instead).
+int run_ragged(int32_t block, double alpha, bool extract, hipStream_t st, int route,
+               int64_t *n_lapack, bool check, uint32_t *sink, const std::vector<tmf::RaggedFrame> &table,
+               const std::vector<RaggedChunk> &chunks)
+{
+    const int64_t nch = (int64_t)chunks.size();
+    if (nch == 0) return 0;
+    int64_t max_blocks = 0;
+    for (const RaggedChunk &c : chunks) max_blocks = std::max(max_blocks, c.blocks);
+    const size_t tbytes = table.size() * sizeof(tmf::RaggedFrame);
+    TableSlot slot;
+    if (int rc = take_table(tbytes, stream_device(st), slot)) return rc;
+    std::copy(table.begin(), table.end(), static_cast<tmf::RaggedFrame *>(slot.p));
+    DevBuf dtable, list, counts;
+    int rc = dtable.alloc(tbytes, st, "frame table");
+    if (rc == 0 && hipMemcpyAsync(dtable.p, slot.p, tbytes, hipMemcpyHostToDevice, st) != hipSuccess)
+        rc = fail(TMFWM_ERR_HIP, "copying the frame table failed: %s", hipGetErrorString(hipGetLastError()));
+    give_table(slot, st);
+    if (rc) return rc;
+    if (max_blocks > 0) {
+        if (int r2 = list.alloc((size_t)max_blocks * 4, st, "dgesdd-route block list")) return r2;
+    }
+    if (int r2 = counts.alloc((size_t)nch * 12, st, "block-list counts")) return r2;  // as run_embed's
+    TMF_HIP(hipMemsetAsync(counts.p, 0, (size_t)nch * 12, st));
+    for (int64_t c = 0; c < nch; ++c) {
+        const RaggedChunk &k = chunks[(size_t)c];
+        tmf::RaggedArgs r{};
+        r.frames = static_cast<const tmf::RaggedFrame *>(dtable.p) + k.first;
+        r.nframes = (int32_t)k.n;
+        r.block = block;
+        r.alpha = alpha;
+        r.alpha32 = (float)alpha;
+        r.fb_list = static_cast<uint32_t *>(list.p);
+        r.fb_count = static_cast<uint32_t *>(counts.p) + c;
+        r.fb_bad = static_cast<uint32_t *>(counts.p) + nch + c;
+        if (k.blocks > 0) {
+            if (route == TMFWM_ROUTE_REFERENCE) TMF_HIP(tmf::launch_list_all(r.fb_list, r.fb_count, k.blocks, st));
+            else TMF_HIP(extract ? tmf::launch_extract_ragged(r, k.waves, st) : tmf::launch_embed_ragged(r, k.waves, st));
+        }
+        if (!extract) TMF_HIP(tmf::launch_edges_ragged(r, k.edge, st));
+        if (k.blocks > 0) {
+            TMF_HIP(extract ? tmf::launch_extract_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st)
+                            : tmf::launch_embed_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st));
+            if (force_nonconv()) TMF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(r.fb_bad), 1, 1, st));
+        }
+    }
+    if (sink) {
+        TMF_HIP(hipMemcpyAsync(sink, counts.p, (size_t)nch * 12, hipMemcpyDeviceToHost, st));
+        return 0;
+    }
+    if (n_lapack || check) return sum_counts(static_cast<const uint32_t *>(counts.p), nch, st, n_lapack);
+    return 0;
+}
+
+size_t round16(size_t n) { return (n + 15) & ~size_t(15); }
+
+int ragged_call(std::vector<RFrame> &fr, int32_t block, double alpha, bool extract, int32_t mem_kind, void *hip_stream, int32_t route,
+                int64_t *n_lapack)
+{
+    for (size_t i = 0; i < fr.size(); ++i)
+        if (int rc = check_ragged_frame((int64_t)i, fr[i], block, extract)) return rc;
+    if (int rc = need_device()) return rc;
+    if (fr.empty()) return 0;
+    hipStream_t st = pick_stream(hip_stream);
+    std::vector<tmf::RaggedFrame> table;
+    std::vector<RaggedChunk> chunks;
+    if (mem_kind == TMFWM_MEM_DEVICE) {
+        if (int rc = check_ragged_device(fr, block, extract)) return rc;
+        plan_ragged(fr, block, extract, table, chunks);
+        return run_ragged(block, alpha, extract, st, route, n_lapack, false, nullptr, table, chunks);
+    }
+    // host memory: every buffer of the call in one device allocation (16-byte aligned pieces),
+    // results copied back, one synchronisation
+    std::vector<RFrame> dv(fr);
+    size_t total = 0;
+    std::vector<size_t> off(fr.size() * 3);
+    for (size_t i = 0; i < fr.size(); ++i) {
+        const size_t px = (size_t)fr[i].pixel_bytes(), tb = (size_t)fr[i].tile_bytes(block);
+        const size_t sz[3] = {px, extract ? px : tb, extract ? tb : px};
+        for (int k = 0; k < 3; ++k) {
+            off[3 * i + k] = total;
+            total += round16(sz[k]);
+        }
+    }
+    DevBuf stage;
+    if (int rc = stage.alloc(total, st, "ragged frames")) return rc;
+    uint8_t *base = static_cast<uint8_t *>(stage.p);
+    for (size_t i = 0; i < fr.size(); ++i) {
+        const size_t px = (size_t)fr[i].pixel_bytes(), tb = (size_t)fr[i].tile_bytes(block);
+        if (px == 0 || (extract && tb == 0)) continue;
+        dv[i].in0 = base + off[3 * i];
+        dv[i].in1 = base + off[3 * i + 1];
+        dv[i].out = base + off[3 * i + 2];
+        TMF_HIP(hipMemcpyAsync(base + off[3 * i], fr[i].in0, px, hipMemcpyHostToDevice, st));
+        if (extract || tb) TMF_HIP(hipMemcpyAsync(base + off[3 * i + 1], fr[i].in1, extract ? px : tb, hipMemcpyHostToDevice, st));
+    }
+    plan_ragged(dv, block, extract, table, chunks);
+    const int64_t nch = (int64_t)chunks.size();
+    HostSink sink(nch, st);
+    if (int rc = run_ragged(block, alpha, extract, st, route, n_lapack, true, sink.p, table, chunks)) return rc;
+    for (size_t i = 0; i < fr.size(); ++i) {
+        const size_t px = (size_t)fr[i].pixel_bytes(), tb = (size_t)fr[i].tile_bytes(block);
+        const size_t ob = extract ? tb : px;
+        if (px == 0 || ob == 0) continue;
+        TMF_HIP(hipMemcpyAsync(fr[i].out, dv[i].out, ob, hipMemcpyDeviceToHost, st));
+    }
+    TMF_HIP(hipStreamSynchronize(st));
+    return sink.p && nch ? tmf::sum_sink(sink.p, nch, n_lapack) : 0;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int tmfwm_embed_ragged(const tmfwm_embed_frame *frames, int64_t n_frames, int32_t block, double alpha, int32_t mem_kind,
+                       void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    t_err.clear();
+    if (int rc = check_ragged_call(frames, n_frames, block, alpha, false, mem_kind, route, n_lapack_blocks)) return rc;
+    std::vector<RFrame> fr((size_t)n_frames);  // the library's copy: the caller's array is not read again
+    for (int64_t i = 0; i < n_frames; ++i) fr[(size_t)i] = {frames[i].rgb, frames[i].wm_tile, frames[i].out, frames[i].height, frames[i].width};
+    return ragged_call(fr, block, alpha, false, mem_kind, hip_stream, route, n_lapack_blocks);
+}
+
+int tmfwm_extract_ragged(const tmfwm_extract_frame *frames, int64_t n_frames, int32_t block, double alpha, int32_t mem_kind,
+                         void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    t_err.clear();
+    if (int rc = check_ragged_call(frames, n_frames, block, alpha, true, mem_kind, route, n_lapack_blocks)) return rc;
+    std::vector<RFrame> fr((size_t)n_frames);
+    for (int64_t i = 0; i < n_frames; ++i)
+        fr[(size_t)i] = {frames[i].wm_rgb, frames[i].orig_rgb, frames[i].out_tile, frames[i].height, frames[i].width};
+    return ragged_call(fr, block, alpha, true, mem_kind, hip_stream, route, n_lapack_blocks);
 }
 
 }  // extern "C"

@@ -1,0 +1,131 @@
+// Ragged batches (tmfwm_embed_ragged / tmfwm_extract_ragged): frames of mixed sizes, each with
+// its own buffers, through one set of launches.
+//
+// The host builds a frame table -- one RaggedFrame per frame, with the exclusive prefix sums of
+// the frames' strip waves, blocks and edge pixels -- and uploads it in one copy.  A ragged
+// kernel finds its frame by binary search in a prefix, builds the EmbedArgs / ExtractArgs of
+// that one frame (nframes = 1, strides 0, no list pass) and calls the device function of the
+// single-size kernel with it, so a frame's bytes are the single-size path's by construction.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "tmfwm_internal.h"
+
+namespace tmf {
+
+struct RaggedFrame {
+    const uint8_t *in0;  // embed: the frame's pixels; extract: the watermarked frame
+    const uint8_t *in1;  // embed: its nbh x nbw tile; extract: the original frame
+    uint8_t *out;        // embed: the output pixels; extract: the nbh x nbw tile
+    int32_t H, W, nbh, nbw, strips_per_row;
+    int32_t aligned;     // as dev_aligned: both pixel buffers 4-byte aligned and W % 4 == 0
+    // exclusive prefix sums over the frames of the chunk (the launches' flat indices):
+    uint32_t wave0;      // strip waves, nbh * strips_per_row per frame
+    uint32_t block0;     // blocks, nbh * nbw per frame: the block-list ids are block0 + bi * nbw + bj
+    int64_t edge0;       // pixels outside the block grid
+};
+static_assert(sizeof(RaggedFrame) == 64, "frame table entry");
+
+struct RaggedArgs {
+    const RaggedFrame *frames;  // the chunk's frames (device memory)
+    int32_t nframes, block;
+    double alpha;               // embed
+    float alpha32;              // extract: f32(alpha), as ExtractArgs
+    uint32_t *fb_list;          // the dgesdd-route list, ids relative to the chunk, as EmbedArgs / ExtractArgs
+    uint32_t *fb_count;
+    uint32_t *fb_bad;
+};
+
+// blocks per strip wave at this block size (Geo<b>::BPW): the host needs it for strips_per_row
+int ragged_strip_blocks(int block);
+// strip pass of a chunk: `waves` = the chunk's strip waves (> 0), one workgroup each
+hipError_t launch_embed_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st);
+hipError_t launch_extract_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st);
+// colour round trip of the chunk's `pixels` edge pixels (embed)
+hipError_t launch_edges_ragged(const RaggedArgs &r, int64_t pixels, hipStream_t st);
+// the dgesdd route over the chunk's list (ids as above), max_entries bounds the list
+hipError_t launch_embed_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
+                                     hipStream_t st);
+hipError_t launch_extract_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
+                                       hipStream_t st);
+
+#if defined(__HIPCC__)
+// The table through the constant address space: a load from it at a wave-uniform address is a
+// scalar load, so what a strip wave reads of its frame stays in SGPRs (the VGPR budget of
+// embed_blocks is spent to the last register, tmfwm_blocks.h).
+#define TMF_CONST_AS __attribute__((address_space(4)))
+using RaggedFrameK = const TMF_CONST_AS RaggedFrame;
+__device__ __forceinline__ RaggedFrameK *ragged_const(const RaggedFrame *p) { return (RaggedFrameK *)p; }
+
+// the frame that owns flat index x: the last i in [0, n) with prefix(i) <= x (frames with
+// nothing to do share their successor's prefix and are never found)
+template <class Prefix>
+__device__ __forceinline__ int ragged_find(int n, uint64_t x, Prefix prefix)
+{
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((uint64_t)prefix(mid) <= x) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// the one-frame views of frame f (a table entry in either address space)
+template <class F>
+__device__ __forceinline__ EmbedArgs ragged_embed_view(const RaggedArgs &r, F *f)
+{
+    EmbedArgs a;
+    a.src = f->in0;
+    a.dst = f->out;
+    a.wm = f->in1;
+    a.wm_stride = 0;
+    a.nframes = 1;
+    a.frame_stride = 0;
+    a.H = f->H;
+    a.W = f->W;
+    a.block = r.block;
+    a.nbh = f->nbh;
+    a.nbw = f->nbw;
+    a.strips_per_row = f->strips_per_row;
+    a.aligned = f->aligned;
+    a.alpha = r.alpha;
+    a.fb_list = r.fb_list;
+    a.fb_count = r.fb_count;
+    a.fb_bad = r.fb_bad;
+    a.slow_list = nullptr;  // no list pass: the strip pass runs every block to the end
+    a.slow_count = nullptr;
+    a.slow_shards = nullptr;
+    return a;
+}
+
+template <class F>
+__device__ __forceinline__ ExtractArgs ragged_extract_view(const RaggedArgs &r, F *f)
+{
+    ExtractArgs a;
+    a.wsrc = f->in0;
+    a.osrc = f->in1;
+    a.out = f->out;
+    a.nframes = 1;
+    a.frame_stride = 0;
+    a.tile_stride = 0;
+    a.H = f->H;
+    a.W = f->W;
+    a.block = r.block;
+    a.nbh = f->nbh;
+    a.nbw = f->nbw;
+    a.strips_per_row = f->strips_per_row;
+    a.aligned = f->aligned;
+    a.alpha32 = r.alpha32;
+    a.fb_list = r.fb_list;
+    a.fb_count = r.fb_count;
+    a.fb_bad = r.fb_bad;
+    a.slow_list = nullptr;  // undecided blocks go straight to the dgesdd route
+    a.slow_count = nullptr;
+    a.slow_shards = nullptr;
+    return a;
+}
+#endif
+
+}  // namespace tmf

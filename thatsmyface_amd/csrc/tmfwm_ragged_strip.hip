@@ -1,0 +1,87 @@
+// Strip passes of the ragged calls (tmfwm_ragged.h) for one block size, TMF_RAGGED_B: the
+// Makefile compiles this file once per size (tmfwm_ragged_strip<b>.o), b = 8 under the same
+// max-ILP scheduler as its single-size sibling embed_kernel<8> (tmfwm_embed8.hip).
+//
+// One workgroup (one wave) per strip on a flat 1-D grid.  The wave finds its frame in the
+// table's wave prefix -- blockIdx.x is wave-uniform, so the search and what it yields are scalar
+// loads and SGPRs -- and runs embed_blocks<B, false> / extract_sigmas<B, kPowerIters> on that
+// frame's one-frame view.
+#include "tmfwm_passes.h"
+#include "tmfwm_ragged.h"
+
+#ifndef TMF_RAGGED_B
+#error "TMF_RAGGED_B: the block size of this translation unit"
+#endif
+
+namespace tmf {
+
+// this wave's strip of frame f (frame index 0 of the one-frame view) and its first block's id
+template <int B>
+TMF_DEVI StripPos ragged_strip_pos(RaggedFrameK *f, uint32_t &id)
+{
+    const uint32_t w = blockIdx.x - f->wave0, spr = (uint32_t)f->strips_per_row;
+    StripPos p;
+    p.frame = 0;
+    p.bi = (int)(w / spr);
+    p.bj = (int)(w % spr) * Geo<B>::BPW + (int)(threadIdx.x & 63) / Geo<B>::L;
+    p.valid = p.bj < f->nbw;
+    id = f->block0 + (uint32_t)p.bi * (uint32_t)f->nbw + (uint32_t)p.bj;
+    return p;
+}
+
+TMF_DEVI RaggedFrameK *ragged_wave_frame(const RaggedArgs &r)
+{
+    RaggedFrameK *tab = ragged_const(r.frames);
+    return tab + ragged_find(r.nframes, blockIdx.x, [&](int i) { return tab[i].wave0; });
+}
+
+template <int B>
+__global__ __launch_bounds__(64, kEmbedWaves<B>) void embed_ragged_kernel(RaggedArgs r)
+{
+    constexpr int BPW = Geo<B>::BPW, TS = kEmbedTS<B>;
+    __shared__ __attribute__((aligned(16))) float lds_all[BPW * TS + kHiPad<B> + kLds2Floats<B>];  // as embed_kernel
+    float *lds = lds_all, *lds2 = lds_all + BPW * TS + kHiPad<B>;
+    RaggedFrameK *f = ragged_wave_frame(r);
+    const EmbedArgs a = ragged_embed_view(r, f);
+    uint32_t id;
+    const StripPos pos = ragged_strip_pos<B>(f, id);
+    embed_blocks<B, false>(a, pos, id, lds, lds2);
+}
+
+template <int B>
+__global__ __launch_bounds__(64, (B > 8 ? 2 : kExtract8Waves)) void extract_ragged_kernel(RaggedArgs r)
+{
+    constexpr int L = Geo<B>::L, BPW = Geo<B>::BPW, LD = B + 1;
+    __shared__ float lds[BPW * B * LD];
+    const int lane = threadIdx.x & 63, g = lane / L, q = lane % L;
+    RaggedFrameK *f = ragged_wave_frame(r);
+    const ExtractArgs a = ragged_extract_view(r, f);
+    uint32_t id;
+    const StripPos pos = ragged_strip_pos<B>(f, id);
+    float sw, so;
+    bool ok;
+    extract_sigmas<B, kPowerIters>(a, pos, lds + g * B * LD, q, sw, so, ok);
+    if (!pos.valid || q != 0) return;
+    if (!ok) {  // the enclosure did not decide f32(sigma_1): the dgesdd route
+        a.fb_list[atomicAdd(a.fb_count, 1u)] = id;
+        return;
+    }
+    a.out[(int64_t)pos.bi * a.nbw + pos.bj] = extract_byte(sw, so, a.alpha32);
+}
+
+#define TMF_CAT_(a, b) a##b
+#define TMF_CAT(a, b) TMF_CAT_(a, b)
+
+hipError_t TMF_CAT(launch_embed_ragged_, TMF_RAGGED_B)(const RaggedArgs &r, unsigned waves, hipStream_t st)
+{
+    hipLaunchKernelGGL((embed_ragged_kernel<TMF_RAGGED_B>), dim3(waves), dim3(64), 0, st, r);
+    return hipGetLastError();
+}
+
+hipError_t TMF_CAT(launch_extract_ragged_, TMF_RAGGED_B)(const RaggedArgs &r, unsigned waves, hipStream_t st)
+{
+    hipLaunchKernelGGL((extract_ragged_kernel<TMF_RAGGED_B>), dim3(waves), dim3(64), 0, st, r);
+    return hipGetLastError();
+}
+
+}  // namespace tmf

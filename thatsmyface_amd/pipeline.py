@@ -10,6 +10,8 @@ what is left.  This module overlaps the three stages:
 * device (one ordered stage): pinned host buffer -> async H2D on a side stream ->
   ``embed_batch`` (one launch) -> async D2H into pinned memory; the watermark tile
   for each image size is prepared once on the device (``tmfwm_prepare_tile``);
+  with ``batch_images=K`` the stage takes up to K decoded images of any sizes at a time and
+  embeds the group with one ``embed_ragged`` (``RaggedGpuStage``);
 * encode (thread pool): waits for the copy, PNG-encodes (zlib releases the GIL).
 
 Results come back in input order and are byte-identical to
@@ -113,8 +115,46 @@ class GpuStage:
         return host_out.numpy()[0], wait
 
 
+class RaggedGpuStage(GpuStage):
+    """Batched device stage (``embed_images(..., batch_images=K)``): a group of decoded images of
+    any sizes is uploaded, each image's tile comes from GpuStage's cached ``prepare_tile``, one
+    ``embed_ragged`` embeds the whole group, and the results are copied back.
+
+    Called as ``stage(rgbs, indices)`` with the group's pixel arrays and their positions in the
+    input (the watermark of image ``i`` is watermark ``i`` when there is one per image); returns
+    one ``(pixels, wait)`` per image, in the group's order."""
+
+    def __call__(self, rgbs, indices):
+        torch = self.torch
+        tiles, host_in, host_out = [], [], []
+        for rgb, index in zip(rgbs, indices):
+            h, w = rgb.shape[:2]
+            nbh, nbw = h // self.block, w // self.block
+            if nbh == 0 or nbw == 0:
+                raise ValueError("height and width must be > 0")  # as GpuStage
+            tiles.append(self._tile(nbh, nbw, index if self.per_image else 0))
+            hi = torch.empty((h, w, 3), dtype=torch.uint8, pin_memory=True)
+            hi.numpy()[...] = rgb
+            host_in.append(hi)
+            host_out.append(torch.empty((h, w, 3), dtype=torch.uint8, pin_memory=True))
+        with torch.cuda.stream(self.stream):
+            dev_in = [h.to(self.device, non_blocking=True) for h in host_in]
+            dev_out = self.batch.embed_ragged(dev_in, tiles, self.block, self.alpha, stream=self.stream, route=self.route)
+            for ho, do in zip(host_out, dev_out):
+                ho.copy_(do, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(self.stream)
+        keep = (dev_in, dev_out, host_in)  # alive until the copies have landed
+
+        def wait(_e=done, _k=keep):
+            _e.synchronize()
+
+        return [(ho.numpy(), wait) for ho in host_out]
+
+
 def embed_images(images: Iterable, watermark_data, preserve_ratio: bool = True, custom_settings: dict | None = None,
-                 workers: int | None = None, device_stage: Callable | None = None) -> list[Embedded]:
+                 workers: int | None = None, device_stage: Callable | None = None,
+                 batch_images: int | None = None) -> list[Embedded]:
     """Embed ``watermark_data`` (PNG bytes or PIL image) into every image (bytes, file
     object or PIL image) -- embed_watermark_page.py:492-558 without the per-image
     serialisation.  Returns, in input order, the watermarked pixels and PNG bytes.
@@ -122,7 +162,13 @@ def embed_images(images: Iterable, watermark_data, preserve_ratio: bool = True, 
     ``watermark_data`` may also be a list or tuple with one watermark per image (a service
     watermarking many users' images: no two QR codes are alike): image i gets watermark i, a
     length mismatch raises ValueError, and a custom ``device_stage`` is called as
-    ``stage(rgb, i)`` instead of ``stage(rgb)``."""
+    ``stage(rgb, i)`` instead of ``stage(rgb)``.
+
+    ``batch_images=K`` makes the device stage take up to K decoded images at a time, of any
+    sizes, and embed each group with one ragged launch set (``RaggedGpuStage``; a custom
+    ``device_stage`` is then called as ``stage(rgbs, indices)`` and returns one
+    ``(pixels, wait)`` per image).  Order, pixels and PNG bytes are those of the per-image path,
+    which ``None`` keeps."""
     settings = custom_settings or {}
     block = int(settings.get("block_size", BLOCK_SIZE))
     alpha = float(settings.get("alpha", ALPHA))
@@ -131,11 +177,22 @@ def embed_images(images: Iterable, watermark_data, preserve_ratio: bool = True, 
     per_image = isinstance(watermark_data, (list, tuple))
     if per_image and len(watermark_data) != len(sources):
         raise ValueError(f"{len(watermark_data)} watermarks for {len(sources)} images")
-    stage = device_stage or GpuStage(watermark_data, block, alpha, preserve_ratio, route=route)
+    if batch_images is not None and int(batch_images) < 1:
+        raise ValueError(f"batch_images must be >= 1 or None, got {batch_images!r}")
+    stage = device_stage or (GpuStage if batch_images is None else RaggedGpuStage)(watermark_data, block, alpha, preserve_ratio,
+                                                                                 route=route)
     n_workers = workers or min(16, max(2, (len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 4)))
     with ThreadPoolExecutor(n_workers, thread_name_prefix="tmf-io") as pool:
         decoded: list[Future] = [pool.submit(_decode, s) for s in sources]
         encoded: list[Future] = []
+        if batch_images is not None:  # the device stage takes groups of decoded images, in order
+            for i0 in range(0, len(decoded), int(batch_images)):
+                indices = list(range(i0, min(i0 + int(batch_images), len(decoded))))
+                results = stage([decoded[i].result() for i in indices], indices)
+                if len(results) != len(indices):
+                    raise ValueError(f"the device stage returned {len(results)} results for {len(indices)} images")
+                encoded.extend(pool.submit(_encode, pixels, wait) for pixels, wait in results)
+            return [f.result() for f in encoded]
         for i, fut in enumerate(decoded):  # the device stage runs in order on this thread
             pixels, wait = stage(fut.result(), i) if per_image else stage(fut.result())
             encoded.append(pool.submit(_encode, pixels, wait))

@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""Ragged batches against the single-size path on the GPU ("Ragged batches").
+
+Workload A (the app's case): 64 camera-like covers with sizes drawn with a fixed seed from
+640 x 480 ... 1920 x 1080, a QR tile per image, b = 8, alpha 0.1, hybrid route, frames resident
+on the device.  One embed_ragged + one extract_ragged against the loop of 64 single-frame
+embed_batch / extract_batch calls.
+
+Workload B (the cost of the frame table and of going without the list pass): 256 frames of
+1920 x 1080 at b = 8 and b = 16, on noise covers and on camera-like covers; embed_ragged against
+embed_batch (a tile per frame) on the same frames.
+
+Both arms of a comparison run alternately in one process, each timing a window of `inner` calls
+that ends in a device synchronise.  Every ratio comes with the A/A spread of its own run: the
+medians of the even and of the odd rounds of the same arm, as a ratio.  The arms' outputs are
+compared byte for byte before anything is timed.
+
+usage: python tools/ragged_bench.py [--workload a|b|ab] [--rounds R] [--frames-b N]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from thatsmyface_amd import batch  # noqa: E402
+
+SIZES = [(480, 640), (600, 800), (768, 1024), (720, 1280), (1080, 1920)]  # (H, W)
+
+
+def window(fn, inner):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(inner):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / inner
+
+
+def compare(name, arms, inner, rounds, extra):
+    """arms: {"base": fn, "ragged": fn}; alternating rounds; prints one JSON line."""
+    for fn in arms.values():  # warm-up: code objects, pools, allocator
+        for _ in range(2):
+            fn()
+    torch.cuda.synchronize()
+    t = {k: [] for k in arms}
+    for _ in range(rounds):
+        for k, fn in arms.items():
+            t[k].append(window(fn, inner))
+    med = {k: statistics.median(v) for k, v in t.items()}
+    aa = {k: statistics.median(v[0::2]) / statistics.median(v[1::2]) for k, v in t.items()}
+    rec = {"workload": name, **extra, "inner": inner, "rounds": rounds,
+           "base_ms": round(1e3 * med["base"], 4), "ragged_ms": round(1e3 * med["ragged"], 4),
+           "ragged_over_base": round(med["ragged"] / med["base"], 4),
+           "aa_base": round(aa["base"], 4), "aa_ragged": round(aa["ragged"], 4),
+           "min_ms": {k: round(1e3 * min(v), 4) for k, v in t.items()}, "max_ms": {k: round(1e3 * max(v), 4) for k, v in t.items()}}
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
+def workload_a(rounds, dev):
+    b, alpha, n = 8, 0.1, 64
+    rng = np.random.default_rng(20240)
+    picks = [SIZES[int(k)] for k in rng.integers(0, len(SIZES), n)]
+    frames = [batch.synth_photo_frames(1, h, w, seed=7000 + i, device=dev)[0].contiguous() for i, (h, w) in enumerate(picks)]
+    tiles = [batch.synth_qr_tile(h // b, w // b, seed=8000 + i, device=dev) for i, (h, w) in enumerate(picks)]
+    frames1 = [f[None] for f in frames]
+    state = {}
+
+    def loop():
+        outs = [batch.embed_batch(f, t, b, alpha) for f, t in zip(frames1, tiles)]
+        state["loop"] = (outs, [batch.extract_batch(o, f, b, alpha) for o, f in zip(outs, frames1)])
+
+    def ragged():
+        outs = batch.embed_ragged(frames, tiles, b, alpha)
+        state["ragged"] = (outs, batch.extract_ragged(outs, frames, b, alpha))
+
+    loop()
+    ragged()
+    torch.cuda.synchronize()
+    for i in range(n):
+        assert torch.equal(state["loop"][0][i][0], state["ragged"][0][i]), ("embed differs", i)
+        assert torch.equal(state["loop"][1][i][0], state["ragged"][1][i]), ("extract differs", i)
+    mp = sum(h * w for h, w in picks) / 1e6
+    sizes = {f"{w}x{h}": picks.count((h, w)) for h, w in SIZES}
+    return compare("A", {"base": loop, "ragged": ragged}, 10, rounds,
+                   {"what": "64 images embed+extract: ragged vs loop of single-frame calls", "block": b, "megapixels": round(mp, 1),
+                    "sizes": sizes, "outputs_equal": True})
+
+
+def workload_b(rounds, dev, n):
+    out = []
+    for cover in ("noise", "photo"):
+        h, w = 1080, 1920
+        frames = batch.synth_photo_frames(n, h, w, device=dev) if cover == "photo" else batch.synth_frames(n, h, w, device=dev)
+        views = [frames[i] for i in range(n)]
+        for b in (8, 16):
+            tiles = torch.stack([batch.synth_tile(h // b, w // b, seed=9000 + i, device=dev) for i in range(n)])
+            tviews = [tiles[i] for i in range(n)]
+            dst = torch.empty_like(frames)
+            dviews = [dst[i] for i in range(n)]
+            ref = batch.embed_batch(frames, tiles, b, 0.1)
+            st_b, st_r = {}, {}
+            batch.embed_batch(frames, tiles, b, 0.1, out=dst, stats=st_b)
+            got = batch.embed_ragged(views, tviews, b, 0.1, out=dviews, stats=st_r)
+            torch.cuda.synchronize()
+            assert torch.equal(torch.stack(got), ref), ("embed differs", cover, b)
+            assert st_b["lapack_blocks"] == st_r["lapack_blocks"], (st_b, st_r)
+            del ref, got
+            arms = {"base": lambda: batch.embed_batch(frames, tiles, b, 0.1, out=dst),
+                    "ragged": lambda: batch.embed_ragged(views, tviews, b, 0.1, out=dviews)}
+            out.append(compare("B", arms, 4, rounds,
+                               {"what": f"{n} x 1080p embed: ragged vs embed_batch", "cover": cover, "block": b,
+                                "lapack_blocks": st_b["lapack_blocks"], "list_pass_blocks_base": st_b["list_pass_blocks"],
+                                "outputs_equal": True}))
+            del tiles, tviews, dst, dviews
+        del frames, views
+        torch.cuda.empty_cache()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", default="ab", choices=("a", "b", "ab"))
+    ap.add_argument("--rounds", type=int, default=10)
+    ap.add_argument("--frames-b", type=int, default=256)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("ragged_bench: no GPU (there is no CPU fallback to time)")
+    dev = torch.device("cuda", 0)
+    print(json.dumps({"device": torch.cuda.get_device_name(0), "rounds": a.rounds}), flush=True)
+    if "a" in a.workload:
+        workload_a(a.rounds, dev)
+    if "b" in a.workload:
+        workload_b(a.rounds, dev, a.frames_b)
+
+
+if __name__ == "__main__":
+    main()
