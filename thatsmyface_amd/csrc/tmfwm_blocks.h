@@ -303,6 +303,30 @@ constexpr bool kReloadBytes = B == 16;
 template <int B, bool LIST>
 constexpr bool kFastTail = TMF_FAST_TAIL && B != 12 && !(LIST && (B == 8 || B == 10 || B == 14));
 
+// The special triplets -- every triplet of a zero block (D == 0), and a triplet whose f32(sigma)
+// is 0 -- take constants for their U and B ends.  true: the ordinary path computes every end
+// without those selects and a wave-uniform branch, taken only when some lane of the wave holds
+// such a triplet, writes the constants over them in the tiles and flags them; false: two-level
+// selects on every end.  Neither case occurs in a noise or camera-like block.  On for b = 8's
+// strip kernels (embed<8> -0.35 % per 4K frame); its list pass and b = 12, 14, 16 would gain
+// scratch or spill more, the other sizes are untimed.
+#ifndef TMF_COLD_SPECIAL
+#define TMF_COLD_SPECIAL true
+#endif
+template <int B, bool LIST>
+constexpr bool kColdSpecial = TMF_COLD_SPECIAL && B == 8 && !LIST;
+
+// Between svd3 and the reconstruction, the work that is the same for every lane of a block
+// (sqrt, 1 / sigma, the gap minima, E_k, the ranks, the S' ends and the blend): true shares the
+// triplets among the block's L lanes, lane q taking k = i L + q, and exchanges the results.
+// On for b = 8's strip kernels (embed<8> -1.6 % per 4K frame); its list pass, b = 12 and the
+// ragged b = 16 kernel would gain scratch or spill more, b = 6 is untimed.
+#ifndef TMF_SPLIT_POST
+#define TMF_SPLIT_POST true
+#endif
+template <int B, bool LIST>
+constexpr bool kSplitPost = TMF_SPLIT_POST && B == 8 && !LIST;
+
 // b = 10 / 14 keep the reconstruction's fma chains in their (k-outer) source order: left free,
 // the compiler regroups them per output element and spills every element of Bm it reads
 // ahead of its use (272 / 282 VGPRs spilled -> 0 / 5; embed<14> 613 -> 360 us per 4K frame,
@@ -368,79 +392,185 @@ TMF_DEVI void embed_blocks(const EmbedArgs &a, const StripPos &pos, uint32_t id,
     }
     __syncthreads();
 
-    // singular values (oracle orc_svd_block: sigma_k = |a_k|, u_k = a_k / sigma_k)
-    double sig[B];
-#pragma unroll
-    for (int k = 0; k < B; ++k) sig[k] = cdot_part<R, B>(A, k, k);
-#pragma unroll
-    for (int k = 0; k < B; ++k) sig[k] = __builtin_sqrt(group_sum<L>(sig[k]));
-    // Conditioning test (oracle orc_svd_flag): m = min over triplets reaching the
-    // output (f32(sigma_k) != 0) of g_k = min(sigma_k, distance to the nearest other sigma); the
-    // block takes the dgesdd route iff m * 2^20 < sigma_1.  (Per-k minima first: folding every
-    // pair into one running minimum is the same value but a 36-deep dependent chain, +1.5 % on
-    // embed<8>, profiles/r03/r03r.)
-    double gk[B], s1 = 0.0;
-#pragma unroll
-    for (int k = 0; k < B; ++k) {
-        gk[k] = sig[k];
-        s1 = sig[k] > s1 ? sig[k] : s1;
-    }
-#pragma unroll
-    for (int k = 0; k < B; ++k)
-#pragma unroll
-        for (int j = k + 1; j < B; ++j) {
-            const double d = __builtin_fabs(sig[k] - sig[j]);
-            gk[k] = d < gk[k] ? d : gk[k];
-            gk[j] = d < gk[j] ? d : gk[j];
-        }
-    double m = s1;
-#pragma unroll
-    for (int k = 0; k < B; ++k) m = ((float)sig[k] != 0.0f && gk[k] < m) ? gk[k] : m;
-    const bool zero = s1 == 0.0;  // N6: D == 0 -> U = I, Vt = I on both routes
-    const bool flag20 = m * 1048576.0 < s1;
-    // Byte certificate: the interval bounds of the blocks whose bytes it decides (zero,
-    // flagged and deferred blocks keep point intervals: the point path's values)
-    const bool cert = !zero && !flat && !flag20 && !slow;
-    const double tE = cert ? kCertScale * s1 : 0.0;
-    // E_k = f32(tE / g_k): in [2^-45, 2^-25] for a certified block (g_k >= 2^-20 s1), held as a float
+    // singular values, gaps, flag, E_k and ranks: per triplet the same for every lane of the block
+    double sig[B], s1, tE;
     float E[B];
-#pragma unroll
-    for (int k = 0; k < B; ++k) E[k] = cert && (float)sig[k] != 0.0f ? (float)(tE / gk[k]) : 0.0f;
-    // Sort descending (oracle: odd-even transposition sort, stable) as ranks: k goes to
-    // position rk[k] = #{j < k: sig[j] >= sig[k]} + #{j > k: sig[j] > sig[k]}.  The
-    // permutation is applied through LDS: U's columns here, Vt's rows with the B store.
     int rk[B];
+    bool zero, flag20, cert;
+    // kSplitPost: the triplets lane q evaluated (k = i L + q), for the U and S' ends further on
+    constexpr int NI = kSplitPost<B, LIST> ? B / L : 1;
+    double osig[NI], oinv[NI];
+    int ork[NI], outbits = 0;  // bit k: f32(sigma_k) != 0
+    if constexpr (kSplitPost<B, LIST>) {
+        // Each lane evaluates the triplets of its share with the expressions of the other branch and
+        // the group exchanges the results (minima, maxima and counts combine exactly in any order)
+        static_assert(L > 1 && B % L == 0, "shares");
+        double tot[B];
 #pragma unroll
-    for (int k = 0; k < B; ++k) rk[k] = 0;
+        for (int k = 0; k < B; ++k) tot[k] = cdot_part<R, B>(A, k, k);
 #pragma unroll
-    for (int k = 1; k < B; ++k)
+        for (int k = 0; k < B; ++k) tot[k] = group_sum<L>(tot[k]);
+        double ogk[NI], os1 = 0.0;
 #pragma unroll
-        for (int j = 0; j < k; ++j) {
-            const int ge = sig[j] >= sig[k] ? 1 : 0;
-            rk[k] += ge;
-            rk[j] += 1 - ge;
+        for (int i = 0; i < NI; ++i) {
+            double t = tot[i * L];
+#pragma unroll
+            for (int j = 1; j < L; ++j) t = q == j ? tot[i * L + j] : t;
+            osig[i] = __builtin_sqrt(t);
+            oinv[i] = 1.0 / osig[i];
+            ogk[i] = osig[i];
+            os1 = osig[i] > os1 ? osig[i] : os1;
         }
+        static_for<B>([&](auto K) { sig[K] = group_bcast<L, K % L>(osig[K / L]); });
+        s1 = group_max<L>(os1);
+        // gaps and ranks of the own triplets against every other one (k' == k: d = 0 is left
+        // out of the minimum; sig > itself is false)
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            ork[i] = 0;
+#pragma unroll
+            for (int k = 0; k < B; ++k) {
+                const double d = __builtin_fabs(osig[i] - sig[k]);
+                const bool other = k / L != i || k % L != q;
+                ogk[i] = other && d < ogk[i] ? d : ogk[i];
+                const bool before = k / L < i || (k / L == i && k % L < q);
+                ork[i] += (before ? sig[k] >= osig[i] : sig[k] > osig[i]) ? 1 : 0;
+            }
+        }
+        double om = s1;
+        int obits = 0;
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const bool out = (float)osig[i] != 0.0f;
+            om = (out && ogk[i] < om) ? ogk[i] : om;
+            obits |= out ? 1 << (i * L) : 0;
+        }
+        outbits = group_or<L>(obits << q);
+        const double m = group_min<L>(om);
+        zero = s1 == 0.0;
+        flag20 = m * 1048576.0 < s1;
+        cert = !zero && !flat && !flag20 && !slow;
+        tE = cert ? kCertScale * s1 : 0.0;
+        float oE[NI];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) oE[i] = cert && (float)osig[i] != 0.0f ? (float)(tE / ogk[i]) : 0.0f;
+        static_for<B>([&](auto K) {
+            E[K] = group_bcast<L, K % L>(oE[K / L]);
+            rk[K] = group_bcast<L, K % L>(ork[K / L]);
+        });
+    } else {
+        // singular values (oracle orc_svd_block: sigma_k = |a_k|, u_k = a_k / sigma_k)
+    #pragma unroll
+        for (int k = 0; k < B; ++k) sig[k] = cdot_part<R, B>(A, k, k);
+    #pragma unroll
+        for (int k = 0; k < B; ++k) sig[k] = __builtin_sqrt(group_sum<L>(sig[k]));
+        // Conditioning test (oracle orc_svd_flag): m = min over triplets reaching the
+        // output (f32(sigma_k) != 0) of g_k = min(sigma_k, distance to the nearest other sigma); the
+        // block takes the dgesdd route iff m * 2^20 < sigma_1.  (Per-k minima first: folding every
+        // pair into one running minimum is the same value but a 36-deep dependent chain, +1.5 % on
+        // embed<8>, profiles/r03/r03r.)
+        double gk[B];
+        s1 = 0.0;
+    #pragma unroll
+        for (int k = 0; k < B; ++k) {
+            gk[k] = sig[k];
+            s1 = sig[k] > s1 ? sig[k] : s1;
+        }
+    #pragma unroll
+        for (int k = 0; k < B; ++k)
+    #pragma unroll
+            for (int j = k + 1; j < B; ++j) {
+                const double d = __builtin_fabs(sig[k] - sig[j]);
+                gk[k] = d < gk[k] ? d : gk[k];
+                gk[j] = d < gk[j] ? d : gk[j];
+            }
+        double m = s1;
+    #pragma unroll
+        for (int k = 0; k < B; ++k) m = ((float)sig[k] != 0.0f && gk[k] < m) ? gk[k] : m;
+        zero = s1 == 0.0;  // N6: D == 0 -> U = I, Vt = I on both routes
+        flag20 = m * 1048576.0 < s1;
+        // Byte certificate: the interval bounds of the blocks whose bytes it decides (zero,
+        // flagged and deferred blocks keep point intervals: the point path's values)
+        cert = !zero && !flat && !flag20 && !slow;
+        tE = cert ? kCertScale * s1 : 0.0;
+        // E_k = f32(tE / g_k): in [2^-45, 2^-25] for a certified block (g_k >= 2^-20 s1), held as a float
+    #pragma unroll
+        for (int k = 0; k < B; ++k) E[k] = cert && (float)sig[k] != 0.0f ? (float)(tE / gk[k]) : 0.0f;
+        // Sort descending (oracle: odd-even transposition sort, stable) as ranks: k goes to
+        // position rk[k] = #{j < k: sig[j] >= sig[k]} + #{j > k: sig[j] > sig[k]}.  The
+        // permutation is applied through LDS: U's columns here, Vt's rows with the B store.
+    #pragma unroll
+        for (int k = 0; k < B; ++k) rk[k] = 0;
+    #pragma unroll
+        for (int k = 1; k < B; ++k)
+    #pragma unroll
+            for (int j = 0; j < k; ++j) {
+                const int ge = sig[j] >= sig[k] ? 1 : 0;
+                rk[k] += ge;
+                rk[j] += 1 - ge;
+            }
+    }
     // U = A / sigma as f32 intervals [f32(u - E), f32(u + E)]; triplets that do not reach the
     // output (f32(sigma) == 0) take U = [2, 2] against B = [-2 S', 2 S'] (|f32 entries| <= 1)
     // over this lane's rows of the triplets that reach the output: an interval that contains 0,
     // an interval that is not a point
     int str = 0, wid = 0;
+    // the triplet reaches the output
+    const auto reaches = [&](int k) {
+        if constexpr (kSplitPost<B, LIST>) return (outbits >> k & 1) != 0;
+        else return (float)sig[k] != 0.0f;
+    };
+    // wave-uniform: some lane holds a special triplet (kColdSpecial)
+    bool special_any = false;
+    if constexpr (kColdSpecial<B, LIST>) {
+        bool sp = zero;
+        if constexpr (kSplitPost<B, LIST>) sp = sp || outbits != (1 << B) - 1;
+        else {
+#pragma unroll
+            for (int k = 0; k < B; ++k) sp = sp || (float)sig[k] == 0.0f;
+        }
+        // (lanes without a block hold a zero block whose results go nowhere)
+        special_any = __builtin_amdgcn_ballot_w64(sp && pos.valid) != 0;
+    }
+    double invs[B];
+    if constexpr (kSplitPost<B, LIST>) static_for<B>([&](auto K) { invs[K] = group_bcast<L, K % L>(oinv[K / L]); });
 #pragma unroll
     for (int k = 0; k < B; ++k) {
-        const double inv = 1.0 / sig[k];
+        double inv;
+        if constexpr (kSplitPost<B, LIST>) inv = invs[k];
+        else inv = 1.0 / sig[k];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             // branch-free (selects): the three cases are lane-divergent
             const double u = A[r][k] * inv;
             float ul = (float)(u - (double)E[k]), uh = (float)(u + (double)E[k]);
             const float id = (q * R + r == k) ? 1.0f : 0.0f;
-            const bool out = (float)sig[k] != 0.0f;  // the triplet reaches the output
-            ul = zero ? id : out ? ul : 2.0f;
-            uh = zero ? id : out ? uh : 2.0f;
-
+            const bool out = reaches(k);
+            if constexpr (!kColdSpecial<B, LIST>) {
+                ul = zero ? id : out ? ul : 2.0f;
+                uh = zero ? id : out ? uh : 2.0f;
+            }
             if (real_row<B>(q, r)) {
                 tile[(q * R + r) * LD + rk[k]] = ul;
                 tile2[(q * R + r) * LD + rk[k]] = uh;
+            }
+        }
+    }
+    if constexpr (kColdSpecial<B, LIST>) {
+        // the constants of the special triplets over what the ordinary path stored for them
+        // (1 / 0 and its NaNs among it)
+        if (special_any) {
+#pragma unroll
+            for (int k = 0; k < B; ++k) {
+                const bool sp = zero || !reaches(k);
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const float c = zero ? ((q * R + r == k) ? 1.0f : 0.0f) : 2.0f;
+                    if (sp && real_row<B>(q, r)) {
+                        tile[(q * R + r) * LD + rk[k]] = c;
+                        tile2[(q * R + r) * LD + rk[k]] = c;
+                    }
+                }
             }
         }
     }
@@ -464,6 +594,33 @@ TMF_DEVI void embed_blocks(const EmbedArgs &a, const StripPos &pos, uint32_t id,
     const double cw = a.alpha * ((double)wv / 255.0);
     float Sl[B], Sh[B];
     bool neg = false;  // alpha < 0 pushing S'[0] below zero: outside the certificate's S' >= 0
+    if constexpr (kSplitPost<B, LIST>) {
+        // the own triplets' ends; the blend once, on the top triplet's (its owner's lane)
+        float oSl[NI], oSh[NI], tl = 0.0f, th = 0.0f;
+        bool mine = false;
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const double lo = osig[i] - tE;
+            oSl[i] = (float)(lo > 0.0 ? lo : 0.0);
+            oSh[i] = (float)(osig[i] + tE);
+            const bool top = ork[i] == 0;
+            tl = top ? oSl[i] : tl;
+            th = top ? oSh[i] : th;
+            mine = mine || top;
+        }
+        const float bl0 = (float)((double)tl + cw), bh0 = (float)((double)th + cw);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const bool top = ork[i] == 0;
+            oSl[i] = top ? bl0 : oSl[i];
+            oSh[i] = top ? bh0 : oSh[i];
+        }
+        neg = group_or<L>(mine && !(bl0 >= 0.0f) ? 1 : 0) != 0;
+        static_for<B>([&](auto K) {
+            Sl[K] = group_bcast<L, K % L>(oSl[K / L]);
+            Sh[K] = group_bcast<L, K % L>(oSh[K / L]);
+        });
+    } else
 #pragma unroll
     for (int k = 0; k < B; ++k) {
         const double lo = sig[k] - tE;
@@ -484,15 +641,38 @@ TMF_DEVI void embed_blocks(const EmbedArgs &a, const StripPos &pos, uint32_t id,
             const float vl = (float)(V[r][k] - (double)E[k]), vh = (float)(V[r][k] + (double)E[k]);
             float bl = vl >= 0.0f ? Sl[k] * vl : Sh[k] * vl;
             float bh = vh <= 0.0f ? Sl[k] * vh : Sh[k] * vh;
-            const float bid = Sl[k] * ((q * R + r == k) ? 1.0f : 0.0f);
-            const bool out = (float)sig[k] != 0.0f;
-            bl = zero ? bid : out ? bl : -2.0f * Sh[k];
-            bh = zero ? bid : out ? bh : 2.0f * Sh[k];
+            const bool out = reaches(k);
+            if constexpr (!kColdSpecial<B, LIST>) {
+                const float bid = Sl[k] * ((q * R + r == k) ? 1.0f : 0.0f);
+                bl = zero ? bid : out ? bl : -2.0f * Sh[k];
+                bh = zero ? bid : out ? bh : 2.0f * Sh[k];
+            }
             if (real_row<B>(q, r)) {
-                str |= (int)(zero || (float)sig[k] != 0.0f) & (int)(bl < 0.0f) & (int)(bh > 0.0f);
-                wid |= (int)(bl != bh);
+                // (cold form: a special triplet's ends are flagged where they are written, below)
+                const bool live = kColdSpecial<B, LIST> ? (!zero && out) : (zero || out);
+                str |= (int)live & (int)(bl < 0.0f) & (int)(bh > 0.0f);
+                wid |= (int)(live || !kColdSpecial<B, LIST>) & (int)(bl != bh);
                 tile[rk[k] * LD + q * R + r] = bl;
                 tile2[rk[k] * LD + q * R + r] = bh;
+            }
+        }
+    }
+    if constexpr (kColdSpecial<B, LIST>) {
+        if (special_any) {
+#pragma unroll
+            for (int k = 0; k < B; ++k) {
+                const bool sp = zero || !reaches(k);
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const float bid = Sl[k] * ((q * R + r == k) ? 1.0f : 0.0f);
+                    const float bl = zero ? bid : -2.0f * Sh[k], bh = zero ? bid : 2.0f * Sh[k];
+                    if (sp && real_row<B>(q, r)) {
+                        str |= (int)zero & (int)(bl < 0.0f) & (int)(bh > 0.0f);
+                        wid |= (int)(bl != bh);
+                        tile[rk[k] * LD + q * R + r] = bl;
+                        tile2[rk[k] * LD + q * R + r] = bh;
+                    }
+                }
             }
         }
     }

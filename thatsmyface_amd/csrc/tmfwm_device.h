@@ -812,6 +812,24 @@ TMF_DEVI int group_or(int v)
     return v;
 }
 
+// minimum / maximum over the L lanes of a group (no NaNs: any order gives the same value)
+template <int L>
+TMF_DEVI double group_min(double v)
+{
+    if constexpr (L >= 2) { const double o = dpp<0xB1>(v); v = o < v ? o : v; }
+    if constexpr (L >= 4) { const double o = dpp<0x4E>(v); v = o < v ? o : v; }
+    if constexpr (L >= 8) { const double o = dpp<0x141>(v); v = o < v ? o : v; }
+    return v;
+}
+template <int L>
+TMF_DEVI double group_max(double v)
+{
+    if constexpr (L >= 2) { const double o = dpp<0xB1>(v); v = o > v ? o : v; }
+    if constexpr (L >= 4) { const double o = dpp<0x4E>(v); v = o > v ? o : v; }
+    if constexpr (L >= 8) { const double o = dpp<0x141>(v); v = o > v ? o : v; }
+    return v;
+}
+
 // exec-style mask of the lanes that are member K of their group
 template <int L, int K>
 constexpr unsigned long long kMemberMask = L == 1 ? ~0ull
