@@ -158,6 +158,34 @@ int tmfwm_extract_route(const uint8_t *wm_rgb, const uint8_t *orig_rgb, int64_t 
                         int64_t frame_stride, int32_t block, double alpha, uint8_t *out_tiles, int32_t mem_kind,
                         void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
 
+/*
+ * Keyed extraction (added within ABI 10; the version number is unchanged and existing entry
+ * points keep their behaviour).  Extract uses the original image for one number per block only:
+ * f32(sigma_1) of the block's DCT.  tmfwm_sigma1_map computes that number for every block of
+ * every frame -- the key: (height/block) x (width/block) float32 per frame, n_frames maps back to
+ * back in out_key -- and tmfwm_extract_keyed extracts from the watermarked frames and a key
+ * instead of the original's pixels.  Its bytes are exactly tmfwm_extract_route's for the original
+ * the key was made from.  A key belongs to one block size and one image size.
+ *
+ * key_stride: bytes between consecutive frames' keys; 0 is one key shared by every frame (one
+ * original, many watermarked copies), any other value must be a multiple of 4 and
+ * >= (height/block)*(width/block)*4 (TMFWM_ERR_INVALID otherwise).  A key entry that is not
+ * finite gives byte 0.
+ *
+ * Routes as tmfwm_extract_route: TMFWM_ROUTE_REFERENCE computes every sigma_1 on the dgesdd
+ * route, the others certify the enclosure and send the undecided blocks there; a key entry is
+ * np.linalg.svd's float32 S[0] on every route, so keys do not depend on the route.
+ * *n_lapack_blocks, tmfwm_last_list_pass_blocks(), the non-convergence report, TMFWM_MEM_HOST
+ * staging and TMFWM_MEM_DEVICE asynchrony as tmfwm_extract_route; with TMFWM_MEM_DEVICE the
+ * output must not overlap an input.  Pixels are 3 bytes (TMFWM_PIX_RGB).
+ */
+int tmfwm_sigma1_map(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
+                     int32_t block, float *out_key, int32_t mem_kind, void *hip_stream, int32_t route,
+                     int64_t *n_lapack_blocks);
+int tmfwm_extract_keyed(const uint8_t *wm_rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
+                        const float *key, int64_t key_stride, int32_t block, double alpha, uint8_t *out_tiles,
+                        int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
+
 /* Pixel layouts of tmfwm_embed_px / tmfwm_extract_px (ABI 8) */
 #define TMFWM_PIX_RGB 3  /* 3 bytes per pixel, R G B (numpy / Image.tobytes order) */
 #define TMFWM_PIX_RGBX 4 /* 4 bytes per pixel, R G B pad: how PIL holds a mode-"RGB" image in memory

@@ -87,6 +87,8 @@ SIGNATURES = {
     "tmfwm_extract_ex": (ctypes.c_int, [_VP, _VP, _I64, _I32, _I32, _I64, _I32, _D, _VP, _I32, _VP, _VP]),
     "tmfwm_embed_route": (ctypes.c_int, [_VP, _I64, _I32, _I32, _I64, _VP, _I32, _D, _VP, _I32, _VP, _I32, _VP]),
     "tmfwm_extract_route": (ctypes.c_int, [_VP, _VP, _I64, _I32, _I32, _I64, _I32, _D, _VP, _I32, _VP, _I32, _VP]),
+    "tmfwm_sigma1_map": (ctypes.c_int, [_VP, _I64, _I32, _I32, _I64, _I32, _VP, _I32, _VP, _I32, _VP]),
+    "tmfwm_extract_keyed": (ctypes.c_int, [_VP, _I64, _I32, _I32, _I64, _VP, _I64, _I32, _D, _VP, _I32, _VP, _I32, _VP]),
     "tmfwm_embed_px": (ctypes.c_int, [_VP, _I32, _I64, _I64, _I32, _I32, _VP, _I32, _D, _VP, _I32, _I64, _I32, _VP, _I32, _VP]),
     "tmfwm_embed_tiles": (ctypes.c_int, [_VP, _I32, _I64, _I64, _I32, _I32, _VP, _I64, _I32, _D, _VP, _I32, _I64, _I32, _VP, _I32, _VP]),
     "tmfwm_embed_ragged": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _VP, _I32, _VP]),

@@ -111,6 +111,66 @@ def extract_batch(wframes: torch.Tensor, oframes: torch.Tensor, block: int = 8, 
     return out
 
 
+def sigma1_map(frames: torch.Tensor, block: int = 8, out: torch.Tensor | None = None, stream=None,
+               stats: dict | None = None, route: str = "hybrid") -> torch.Tensor:
+    """The extraction key of every frame: float32 (N, H//b, W//b), f32(sigma_1) of each block's
+    DCT -- all that extract uses of an original image.  The key is the same bit
+    for bit on every route.  stats and route as extract_batch's."""
+    _check_frames(frames, "frames")
+    n, h, w, _ = frames.shape
+    if block not in SUPPORTED_BLOCK_SIZES:
+        raise NotImplementedError(f"block {block}")
+    shape = (n, h // block, w // block)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=frames.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != frames.device or not out.is_contiguous():
+        raise ValueError(f"out must be {shape} float32, contiguous, on the frames' device")
+    cnt, ptr = _count_ptr(stats)
+    with torch.cuda.device(frames.device):
+        L = _lib.load()
+        _lib.check(L.tmfwm_sigma1_map(frames.data_ptr(), n, h, w, h * w * 3, block, out.data_ptr(), _lib.MEM_DEVICE,
+                                      _stream(stream), _lib.route_code(route), ptr), "sigma1_map")
+    if stats is not None:
+        stats["lapack_blocks"] = int(cnt.value)
+        stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks())
+    return out
+
+
+def extract_keyed(wframes: torch.Tensor, key: torch.Tensor, block: int = 8, alpha: float = 0.1,
+                  out: torch.Tensor | None = None, stream=None, stats: dict | None = None,
+                  route: str = "hybrid") -> torch.Tensor:
+    """extract_batch without the original frames: key is sigma1_map of the original(s), (H//b, W//b)
+    shared by every frame (one original, many watermarked copies) or (N, H//b, W//b).  The
+    bytes are extract_batch's.  A key belongs to one block size and one image size.  stats and
+    route as extract_batch's."""
+    _check_frames(wframes, "wframes")
+    n, h, w, _ = wframes.shape
+    if block not in SUPPORTED_BLOCK_SIZES:
+        raise NotImplementedError(f"block {block}")
+    nbh, nbw = h // block, w // block
+    if not isinstance(key, torch.Tensor) or key.dtype != torch.float32:
+        raise TypeError("key must be a float32 tensor")
+    if tuple(key.shape) not in ((nbh, nbw), (n, nbh, nbw)):
+        raise ValueError(f"key must be ({nbh}, {nbw}) or ({n}, {nbh}, {nbw}) for block {block} and {w}x{h} frames, "
+                         f"got {tuple(key.shape)}: a key belongs to one block size and one image size")
+    if key.device != wframes.device or not key.is_contiguous():
+        raise ValueError("key must be contiguous and on the frames' device")
+    if out is None:
+        out = torch.empty((n, nbh, nbw), dtype=torch.uint8, device=wframes.device)
+    elif tuple(out.shape) != (n, nbh, nbw) or out.dtype != torch.uint8 or out.device != wframes.device or not out.is_contiguous():
+        raise ValueError(f"out must be ({n}, {nbh}, {nbw}) uint8, contiguous, on the frames' device")
+    cnt, ptr = _count_ptr(stats)
+    with torch.cuda.device(wframes.device):
+        L = _lib.load()
+        _lib.check(L.tmfwm_extract_keyed(wframes.data_ptr(), n, h, w, h * w * 3, key.data_ptr(),
+                                         0 if key.dim() == 2 else nbh * nbw * 4, block, float(alpha), out.data_ptr(),
+                                         _lib.MEM_DEVICE, _stream(stream), _lib.route_code(route), ptr), "extract_keyed")
+    if stats is not None:
+        stats["lapack_blocks"] = int(cnt.value)
+        stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks())
+    return out
+
+
 def _check_ragged(frames, name: str, device=None):
     """A sequence of (H_i, W_i, 3) uint8 contiguous GPU tensors on one device -> (list, device)."""
     frames = list(frames)

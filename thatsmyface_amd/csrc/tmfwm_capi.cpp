@@ -423,6 +423,76 @@ int run_extract(ExtractArgs a, hipStream_t st, int64_t *n_lapack, bool check, ui
     if (n_lapack || check) return sum_counts(static_cast<const uint32_t *>(counts.p), ch.n, st, n_lapack);
     return 0;
 }
+
+// Keyed extraction over device-resident frames (a.src, and a.key_out for the map or a.key / a.out
+// for the extract, set): run_extract's chunks, lists, counts and reporting, on one image per frame.
+int run_keyed(KeyedArgs a, bool map, hipStream_t st, int64_t *n_lapack, bool check, uint32_t *sink, int route)
+{
+    Chunks ch;
+    ch.plan(a.nframes, (int64_t)a.nbh * a.nbw);
+    if (ch.cap == 0) {
+        if (sink) std::fill(sink, sink + 3 * ch.n, 0u);
+        if (n_lapack) {
+            *n_lapack = 0;
+            t_list_pass = 0;
+        }
+        return 0;
+    }
+    DevBuf list, slow, shards, counts;
+    if (int rc = list.alloc((size_t)ch.cap * 4, st, "dgesdd-route block list")) return rc;
+    if (route != TMFWM_ROUTE_REFERENCE) {  // the certified path, as extract's on every other route
+        if (int rc = slow.alloc((size_t)ch.cap * 4, st, "list-pass block list")) return rc;
+        if (int rc = shards.alloc((size_t)kListShards * kShardStride * 4, st, "list-pass segment counters")) return rc;
+    }
+    if (int rc = counts.alloc((size_t)ch.n * 12, st, "block-list counts")) return rc;  // as run_embed's
+    TMF_HIP(hipMemsetAsync(counts.p, 0, (size_t)ch.n * 12, st));
+    for (int64_t c = 0; c < ch.n; ++c) {
+        KeyedArgs k = a;
+        const int64_t f0 = c * ch.frames;
+        k.nframes = a.nframes - f0 < ch.frames ? a.nframes - f0 : ch.frames;
+        k.src = a.src + f0 * a.frame_stride;
+        if (map) k.key_out = a.key_out + f0 * a.key_stride;
+        else {
+            k.key = a.key + f0 * a.key_stride;  // stride 0: the one shared key
+            k.out = a.out + f0 * a.tile_stride;
+        }
+        k.fb_list = static_cast<uint32_t *>(list.p);
+        k.fb_count = static_cast<uint32_t *>(counts.p) + c;
+        k.fb_bad = static_cast<uint32_t *>(counts.p) + ch.n + c;
+        k.slow_list = static_cast<uint32_t *>(slow.p);
+        k.slow_count = static_cast<uint32_t *>(counts.p) + 2 * ch.n + c;
+        k.slow_shards = static_cast<uint32_t *>(shards.p);
+        if (shards.p) TMF_HIP(hipMemsetAsync(shards.p, 0, (size_t)kListShards * kShardStride * 4, st));
+        if (route == TMFWM_ROUTE_REFERENCE) TMF_HIP(launch_list_all(k.fb_list, k.fb_count, k.nframes * ch.per_frame, st));
+        else TMF_HIP(map ? launch_sigma1_map(k, st) : launch_extract_keyed(k, st));
+        TMF_HIP(map ? launch_sigma1_fixup(k, k.fb_list, k.fb_count, k.nframes * ch.per_frame, st)
+                    : launch_extract_keyed_fixup(k, k.fb_list, k.fb_count, k.nframes * ch.per_frame, st));
+        if (force_nonconv()) TMF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(k.fb_bad), 1, 1, st));
+    }
+    if (sink) {
+        TMF_HIP(hipMemcpyAsync(sink, counts.p, (size_t)ch.n * 12, hipMemcpyDeviceToHost, st));
+        return 0;
+    }
+    if (n_lapack || check) return sum_counts(static_cast<const uint32_t *>(counts.p), ch.n, st, n_lapack);
+    return 0;
+}
+
+KeyedArgs keyed_args(int64_t n, int32_t H, int32_t W, int64_t stride, int32_t block, double alpha)
+{
+    KeyedArgs a{};
+    a.nframes = n;
+    a.frame_stride = stride;
+    a.tile_stride = (int64_t)(H / block) * (W / block);
+    a.key_stride = a.tile_stride;
+    a.H = H;
+    a.W = W;
+    a.block = block;
+    a.nbh = H / block;
+    a.nbw = W / block;
+    a.alpha32 = (float)alpha;
+    return a;
+}
+
 EmbedArgs embed_args(int64_t n, int32_t H, int32_t W, int64_t stride, int32_t block, double alpha)
 {
     EmbedArgs a{};
@@ -670,6 +740,109 @@ int tmfwm_extract(const uint8_t *wm_rgb, const uint8_t *orig_rgb, int64_t n_fram
 {
     return tmfwm_extract_ex(wm_rgb, orig_rgb, n_frames, height, width, frame_stride, block, alpha, out_tiles, mem_kind,
                             hip_stream, nullptr);
+}
+
+// ---- keyed extraction (within ABI 10): the original's per-block f32 sigma_1 as a key
+int tmfwm_sigma1_map(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride, int32_t block,
+                     float *out_key, int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    t_err.clear();
+    if (route < TMFWM_ROUTE_HYBRID || route > TMFWM_ROUTE_RANK1_REFERENCE) return fail(TMFWM_ERR_INVALID, "route %d", route);
+    if (n_lapack_blocks) {
+        *n_lapack_blocks = 0;
+        t_list_pass = 0;
+    }
+    if (int rc = check_frames(n_frames, height, width, frame_stride, block)) return rc;
+    if (int rc = need_device()) return rc;
+    const int64_t kbytes = (int64_t)(height / block) * (width / block) * 4;
+    if (n_frames == 0 || kbytes == 0) return 0;
+    const size_t span = span_bytes(n_frames, frame_stride, (int64_t)height * width * 3), obytes = (size_t)(kbytes * n_frames);
+    hipStream_t st = pick_stream(hip_stream);
+    tmf::KeyedArgs a = tmf::keyed_args(n_frames, height, width, frame_stride, block, 1.0);
+    if (mem_kind == TMFWM_MEM_DEVICE) {
+        if (int rc = check_device_ptr(rgb, "rgb")) return rc;
+        if (int rc = check_device_ptr(out_key, "out_key")) return rc;
+        if (reinterpret_cast<uintptr_t>(out_key) % 4) return fail(TMFWM_ERR_INVALID, "out_key is not 4-byte aligned");
+        if (ranges_overlap(out_key, obytes, rgb, span)) return fail(TMFWM_ERR_INVALID, "out_key overlaps the input batch");
+        a.src = rgb;
+        a.key_out = out_key;
+        a.aligned = tmf::dev_aligned(rgb, rgb, frame_stride, width);
+        return tmf::run_keyed(a, true, st, n_lapack_blocks, false, nullptr, route);
+    }
+    if (mem_kind != TMFWM_MEM_HOST) return fail(TMFWM_ERR_INVALID, "mem_kind %d", mem_kind);
+    if (!rgb || !out_key) return fail(TMFWM_ERR_INVALID, "NULL host pointer");
+    DevBuf din, dkey;
+    if (int rc = din.alloc(span, st, "frames")) return rc;
+    if (int rc = dkey.alloc(obytes, st, "sigma_1 key maps")) return rc;
+    TMF_HIP(hipMemcpyAsync(din.p, rgb, span, hipMemcpyHostToDevice, st));
+    a.src = static_cast<const uint8_t *>(din.p);
+    a.key_out = static_cast<float *>(dkey.p);
+    a.aligned = frame_stride % 4 == 0 && width % 4 == 0;
+    const int64_t nch = tmf::count_chunks(n_frames, height, width, block);
+    HostSink sink(nch, st);
+    if (int rc = tmf::run_keyed(a, true, st, n_lapack_blocks, true, sink.p, route)) return rc;
+    TMF_HIP(hipMemcpyAsync(out_key, dkey.p, obytes, hipMemcpyDeviceToHost, st));
+    TMF_HIP(hipStreamSynchronize(st));
+    return sink.p ? tmf::sum_sink(sink.p, nch, n_lapack_blocks) : 0;
+}
+
+int tmfwm_extract_keyed(const uint8_t *wm_rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
+                        const float *key, int64_t key_stride, int32_t block, double alpha, uint8_t *out_tiles, int32_t mem_kind,
+                        void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    t_err.clear();
+    if (route < TMFWM_ROUTE_HYBRID || route > TMFWM_ROUTE_RANK1_REFERENCE) return fail(TMFWM_ERR_INVALID, "route %d", route);
+    if (n_lapack_blocks) {
+        *n_lapack_blocks = 0;
+        t_list_pass = 0;
+    }
+    if (int rc = check_frames(n_frames, height, width, frame_stride, block)) return rc;
+    if (!std::isfinite(alpha) || alpha == 0.0) return fail(TMFWM_ERR_INVALID, "alpha must be finite and non-zero");
+    const int64_t tbytes = (int64_t)(height / block) * (width / block), kbytes = tbytes * 4;
+    if (key_stride < 0 || key_stride % 4 != 0 || (key_stride != 0 && key_stride < kbytes))
+        return fail(TMFWM_ERR_INVALID, "key_stride %lld: 0 (one shared key) or a multiple of 4 >= (H/block)*(W/block)*4 = %lld",
+                    (long long)key_stride, (long long)kbytes);
+    if (int rc = need_device()) return rc;
+    if (n_frames == 0 || tbytes == 0) return 0;
+    const size_t span = span_bytes(n_frames, frame_stride, (int64_t)height * width * 3), obytes = (size_t)(tbytes * n_frames);
+    const size_t kspan = (size_t)((key_stride ? (n_frames - 1) * key_stride : 0) + kbytes);
+    hipStream_t st = pick_stream(hip_stream);
+    tmf::KeyedArgs a = tmf::keyed_args(n_frames, height, width, frame_stride, block, alpha);
+    if (mem_kind == TMFWM_MEM_DEVICE) {
+        if (int rc = check_device_ptr(wm_rgb, "wm_rgb")) return rc;
+        if (int rc = check_device_ptr(key, "key")) return rc;
+        if (int rc = check_device_ptr(out_tiles, "out_tiles")) return rc;
+        if (reinterpret_cast<uintptr_t>(key) % 4) return fail(TMFWM_ERR_INVALID, "key is not 4-byte aligned");
+        if (ranges_overlap(out_tiles, obytes, wm_rgb, span) || ranges_overlap(out_tiles, obytes, key, kspan))
+            return fail(TMFWM_ERR_INVALID, "out_tiles overlaps an input");
+        a.src = wm_rgb;
+        a.key = key;
+        a.key_stride = key_stride / 4;
+        a.out = out_tiles;
+        a.aligned = tmf::dev_aligned(wm_rgb, wm_rgb, frame_stride, width);
+        return tmf::run_keyed(a, false, st, n_lapack_blocks, false, nullptr, route);
+    }
+    if (mem_kind != TMFWM_MEM_HOST) return fail(TMFWM_ERR_INVALID, "mem_kind %d", mem_kind);
+    if (!wm_rgb || !key || !out_tiles) return fail(TMFWM_ERR_INVALID, "NULL host pointer");
+    DevBuf dw, dkey, dout;
+    const size_t nk = key_stride ? (size_t)n_frames : 1;  // staged compact
+    if (int rc = dw.alloc(span, st, "watermarked frames")) return rc;
+    if (int rc = dkey.alloc((size_t)kbytes * nk, st, "sigma_1 key maps")) return rc;
+    if (int rc = dout.alloc(obytes, st, "extracted tiles")) return rc;
+    TMF_HIP(hipMemcpyAsync(dw.p, wm_rgb, span, hipMemcpyHostToDevice, st));
+    if (nk == 1 || key_stride == kbytes) TMF_HIP(hipMemcpyAsync(dkey.p, key, (size_t)kbytes * nk, hipMemcpyHostToDevice, st));
+    else TMF_HIP(hipMemcpy2DAsync(dkey.p, (size_t)kbytes, key, (size_t)key_stride, (size_t)kbytes, nk, hipMemcpyHostToDevice, st));
+    a.src = static_cast<const uint8_t *>(dw.p);
+    a.key = static_cast<const float *>(dkey.p);
+    a.key_stride = key_stride ? tbytes : 0;
+    a.out = static_cast<uint8_t *>(dout.p);
+    a.aligned = frame_stride % 4 == 0 && width % 4 == 0;
+    const int64_t nch = tmf::count_chunks(n_frames, height, width, block);
+    HostSink sink(nch, st);
+    if (int rc = tmf::run_keyed(a, false, st, n_lapack_blocks, true, sink.p, route)) return rc;
+    TMF_HIP(hipMemcpyAsync(out_tiles, dout.p, obytes, hipMemcpyDeviceToHost, st));
+    TMF_HIP(hipStreamSynchronize(st));
+    return sink.p ? tmf::sum_sink(sink.p, nch, n_lapack_blocks) : 0;
 }
 
 // ---- 4-byte pixels (ABI 8): the core runs on compact RGB device buffers; RGBX inputs are

@@ -67,6 +67,30 @@ struct ExtractArgs {
     uint32_t *slow_shards;
 };
 
+// Keyed extraction (tmfwm_keyed.hip): one image per frame.  The map pass stores
+// f32(sigma_1) of every block of `src` into key_out; the keyed extract reads the original's
+// sigma_1 from `key` instead of recomputing it from the original's pixels.
+struct KeyedArgs {
+    const uint8_t *src;      // map: the original frames; extract: the watermarked frames
+    const float *key;        // extract: nbh x nbw f32 per frame, key_stride floats apart (0: one key for all frames)
+    float *key_out;          // map: nframes x (nbh x nbw) f32, key_stride floats apart
+    uint8_t *out;            // extract: nframes x (nbh x nbw), tile_stride bytes apart
+    int64_t nframes;
+    int64_t frame_stride;
+    int64_t tile_stride;
+    int64_t key_stride;      // in floats
+    int H, W, block, nbh, nbw, strips_per_row;
+    int aligned;
+    float alpha32;
+    // the lists and counters of ExtractArgs, used the same way
+    uint32_t *fb_list;
+    uint32_t *fb_count;
+    uint32_t *fb_bad;
+    uint32_t *slow_list;
+    uint32_t *slow_count;
+    uint32_t *slow_shards;
+};
+
 struct EdgeArgs {
     const uint8_t *src;
     uint8_t *dst;
@@ -106,6 +130,12 @@ hipError_t launch_dct2d_blocks(float *blocks, int64_t nb, int block, int inverse
 // second pass on the dgesdd route (tmfwm_fallback.hip); max_entries bounds the list
 hipError_t launch_embed_fixup(const EmbedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
 hipError_t launch_extract_fixup(const ExtractArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
+// keyed extraction (tmfwm_keyed.hip; the dgesdd-route passes per block size: tmfwm_keyed_fixup.hip)
+hipError_t launch_sigma1_map(const KeyedArgs &a, hipStream_t st);
+hipError_t launch_extract_keyed(const KeyedArgs &a, hipStream_t st);
+hipError_t launch_sigma1_fixup(const KeyedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
+hipError_t launch_extract_keyed_fixup(const KeyedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries,
+                                      hipStream_t st);
 // the reference route: list = 0 .. n-1, *count = n (every block of a launch on the dgesdd route)
 hipError_t launch_list_all(uint32_t *list, uint32_t *count, int64_t n, hipStream_t st);
 // RGBX (4 bytes per pixel, PIL's in-memory "RGB") <-> RGB (3 bytes) per frame (tmfwm_pixels.hip);

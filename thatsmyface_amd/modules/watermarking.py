@@ -5,6 +5,8 @@ from ..watermarking import (  # noqa: F401
     apply_idct_to_block,
     embed_watermark,
     extract_watermark,
+    extract_watermark_keyed,
+    extraction_key,
     get_watermark_settings,
     resize_watermark,
     rgb_to_ycbcr,

@@ -41,6 +41,8 @@ __all__ = [
     "resize_watermark",
     "embed_watermark",
     "extract_watermark",
+    "extraction_key",
+    "extract_watermark_keyed",
 ]
 
 
@@ -394,5 +396,60 @@ def extract_watermark(watermarked_image, original_image, custom_settings=None):
         L.tmfwm_extract_route(_ptr(w), _ptr(o), 1, height, width, w.size, block_size, float(alpha), _ptr(out), _lib.MEM_HOST,
                               None, route, None),
         "extract_watermark",
+    )
+    return Image.fromarray(out)
+
+
+def _block_size(custom_settings):
+    block_size, alpha = _settings(custom_settings)
+    block_size = int(block_size)
+    if block_size <= 0:
+        raise ValueError(f"block_size must be positive, got {block_size}")
+    return block_size, alpha
+
+
+def extraction_key(original_image, custom_settings=None) -> np.ndarray:
+    """All that extract_watermark uses of the original image (:279-285): float32 (H//b, W//b),
+    f32(sigma_1) of each block's DCT.  Store it (np.save) instead of the original and extract
+    with extract_watermark_keyed.  A key belongs to one block size and one image size."""
+    block_size, _ = _block_size(custom_settings)
+    o = np.ascontiguousarray(np.asarray(_rgb_image(original_image), dtype=np.uint8))
+    height, width = o.shape[:2]
+    nbh, nbw = height // block_size, width // block_size
+    key = np.empty((nbh, nbw), np.float32)
+    if nbh == 0 or nbw == 0:
+        return key
+    L = _lib.load()
+    _lib.check(
+        L.tmfwm_sigma1_map(_ptr(o), 1, height, width, o.size, block_size, _ptr(key), _lib.MEM_HOST, None, _route(custom_settings),
+                           None),
+        "extraction_key",
+    )
+    return key
+
+
+def extract_watermark_keyed(watermarked_image, key, custom_settings=None):
+    """extract_watermark with extraction_key(original_image) in place of the original image:
+    the same (W/b) x (H/b) mode-"L" image, pixel for pixel."""
+    block_size, alpha = _block_size(custom_settings)
+    if not isinstance(key, np.ndarray) or key.dtype != np.float32:
+        raise TypeError(f"key must be a float32 numpy array (extraction_key's result), got {getattr(key, 'dtype', type(key))}")
+    w = np.ascontiguousarray(np.asarray(_rgb_image(watermarked_image), dtype=np.uint8))
+    height, width = w.shape[:2]
+    nbh, nbw = height // block_size, width // block_size
+    if key.shape != (nbh, nbw):
+        raise ValueError(
+            f"key shape {key.shape} != ({nbh}, {nbw}) for a {width}x{height} image at block size {block_size}: "
+            "a key belongs to one block size and one image size"
+        )
+    if nbh == 0 or nbw == 0:
+        return Image.fromarray(np.zeros((nbh, nbw), np.uint8))
+    key = np.ascontiguousarray(key)
+    out = np.empty((nbh, nbw), np.uint8)
+    L = _lib.load()
+    _lib.check(
+        L.tmfwm_extract_keyed(_ptr(w), 1, height, width, w.size, _ptr(key), 0, block_size, float(alpha), _ptr(out), _lib.MEM_HOST,
+                              None, _route(custom_settings), None),
+        "extract_watermark_keyed",
     )
     return Image.fromarray(out)
