@@ -3,6 +3,9 @@
 // workspace of exactly ws_doubles_for<want_v>(n) doubles, the size the fixup kernels give it in LDS --
 // is its own heap allocation of exactly its size, so any read or write past an end aborts.
 // Built and run by tests/test_lapack_device_code.py::test_workspace_bounds_asan; never shipped.
+//
+//   lp_asan [FILE N]...   extra cases: FILE holds raw float32 N x N blocks (row-major, back to back);
+//                         every block runs through the same checks, counted in fields of their own
 #include "../../thatsmyface_amd/csrc/tmfwm_lapack.h"
 
 #include <cmath>
@@ -24,8 +27,14 @@ static double uni()
 
 // cover-like test matrices: 0 noise, 1 rank-deficient (repeated columns), 2 zero,
 // 3 tiny scale, 4 small integers (ties), 5 one nonzero, 6 huge scale, 7 graded rows
+static const float *g_block = nullptr;  // a block of a case file instead of a generated one
+
 static void fill(float *D, int n, int kind)
 {
+    if (g_block) {
+        std::memcpy(D, g_block, sizeof(float) * n * n);
+        return;
+    }
     for (int i = 0; i < n; ++i)
         for (int j = 0; j < n; ++j) {
             double v = 2.0 * uni() - 1.0;
@@ -87,7 +96,24 @@ static int run_compact(int n, int kind)
     return bad;
 }
 
-int main()
+// every block of a case file: both host policies, with and without vectors, and the compact layout
+static bool run_file(const char *path, int n, int &cases, int &bad, int &compact_bad)
+{
+    std::FILE *f = std::fopen(path, "rb");
+    if (!f || n < 1 || n > kMaxN) return false;
+    std::vector<float> blk((size_t)n * n);
+    while (std::fread(blk.data(), sizeof(float), blk.size(), f) == blk.size()) {
+        g_block = blk.data();
+        for (int v = 0; v < 2; ++v) bad += (run<SerialPar>(n, 0, v) != 0) + (run<ReversePar>(n, 0, v) != 0);
+        compact_bad += run_compact<SerialPar>(n, 0) + run_compact<ReversePar>(n, 0);
+        ++cases;
+    }
+    g_block = nullptr;
+    std::fclose(f);
+    return true;
+}
+
+int main(int argc, char **argv)
 {
     int cases = 0, bad = 0;
     for (int n = 1; n <= kMaxN; ++n)
@@ -104,6 +130,18 @@ int main()
             compact_bad += run_compact<SerialPar>(n, kind) + run_compact<ReversePar>(n, kind);
             compact_cases += 2;
         }
+    if (argc > 1) {
+        int file_cases = 0, file_bad = 0, file_compact_bad = 0;
+        for (int a = 1; a + 1 < argc; a += 2)
+            if (!run_file(argv[a], std::atoi(argv[a + 1]), file_cases, file_bad, file_compact_bad)) {
+                std::fprintf(stderr, "lp_asan: cannot read %s as blocks of size %s\n", argv[a], argv[a + 1]);
+                return 2;
+            }
+        std::printf("{\"cases\": %d, \"not_converged\": %d, \"compact_cases\": %d, \"compact_mismatches\": %d, "
+                    "\"file_cases\": %d, \"file_not_converged\": %d, \"file_compact_mismatches\": %d}\n",
+                    cases, bad, compact_cases, compact_bad, file_cases, file_bad, file_compact_bad);
+        return 0;
+    }
     std::printf("{\"cases\": %d, \"not_converged\": %d, \"compact_cases\": %d, \"compact_mismatches\": %d}\n", cases, bad,
                 compact_cases, compact_bad);
     return 0;

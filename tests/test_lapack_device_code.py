@@ -81,21 +81,50 @@ def test_tolerance_constant_is_glibc_pow():
     assert m and float.fromhex(m.group(1)) == (2.0**-53) ** -0.125
 
 
-def test_workspace_bounds_asan(tmp_path):
+@pytest.fixture(scope="module")
+def asan_exe(tmp_path_factory):
+    """tests/native/lp_asan.cpp, a stand-alone host program, built under AddressSanitizer."""
+    if not os.path.exists(HIPCC) and not shutil.which("hipcc"):
+        pytest.skip("hipcc not available")
+    exe = tmp_path_factory.mktemp("lp_asan") / "lp_asan"
+    src = os.path.join(ROOT, "tests", "native", "lp_asan.cpp")
+    subprocess.run([HIPCC, "-x", "hip", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-ffp-contract=off",
+                    "-Xarch_host", "-fsanitize=address", "-fno-omit-frame-pointer", src, "-o", str(exe)], check=True)
+    return str(exe)
+
+
+def test_workspace_bounds_asan(asan_exe):
     """The route's workspace indexing stays inside ws_doubles(n) -- the LDS size the fixup
     kernels give it -- for every n = 1..16 and eight input classes (noise, rank-deficient,
     zero, tiny / huge scale, ties, a single entry, graded rows), under both host policies:
     tests/native/lp_asan.cpp under AddressSanitizer, every array its own exact-size heap
     allocation (the b = 16 fault of the round-2 serial code)."""
-    if not os.path.exists(HIPCC) and not shutil.which("hipcc"):
-        pytest.skip("hipcc not available")
-    exe = tmp_path / "lp_asan"
-    src = os.path.join(ROOT, "tests", "native", "lp_asan.cpp")
-    subprocess.run([HIPCC, "-x", "hip", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-ffp-contract=off",
-                    "-Xarch_host", "-fsanitize=address", "-fno-omit-frame-pointer", src, "-o", str(exe)], check=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600,
+    r = subprocess.run([asan_exe], capture_output=True, text=True, timeout=600,
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1"))
     assert r.returncode == 0, r.stderr[-3000:]
     assert '"cases": 2048' in r.stdout and '"not_converged": 0' in r.stdout, r.stdout
     # the compact workspace of the b > 8 embed pass: in bounds, same bits as the standard layout
     assert '"compact_cases": 256' in r.stdout and '"compact_mismatches": 0' in r.stdout, r.stdout
+    assert "file_cases" not in r.stdout  # without arguments the output is the generated cases' alone
+
+
+def test_workspace_bounds_asan_corpus(asan_exe, tmp_path):
+    """The same program on tests/lp_corpus.py's blocks (every branch of the route the coverage
+    tool finds reachable, tools/lp_coverage.py), handed over as files of raw float32 blocks: in
+    bounds at every b, dbdsqr converged, the compact layout's bits those of the standard one."""
+    import json
+
+    import lp_corpus as C
+
+    args, total = [], 0
+    for b in C.ALL_B:
+        D = np.concatenate([C.matrices(b)[0], C.bidiagonals(b)[0]])
+        D.tofile(tmp_path / f"blocks_{b}.f32")
+        args += [str(tmp_path / f"blocks_{b}.f32"), str(b)]
+        total += len(D)
+    r = subprocess.run([asan_exe, *args], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1"))
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads(r.stdout)
+    assert out["file_cases"] == total and out["file_not_converged"] == 0 and out["file_compact_mismatches"] == 0, out
+    assert out["cases"] == 2048 and out["not_converged"] == 0 and out["compact_mismatches"] == 0, out
