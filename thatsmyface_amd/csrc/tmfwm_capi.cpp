@@ -162,19 +162,31 @@ int check_tile_stride(int64_t tile_stride, int64_t tbytes)
     return 0;
 }
 
-// Host tiles (tile_stride apart; 0: one tile) staged into `buf` in one copy, compact; *dstride is
-// the stride the kernels then use.
+// n items of `bytes` each, `stride` bytes apart in host memory (0: one item shared by all), to or
+// from compact device memory in one copy; the caller's bytes between the items are not touched.
+size_t item_count(int64_t n, int64_t stride) { return stride ? (size_t)n : 1; }
+
+int copy_items(void *dev, const void *host, size_t bytes, int64_t n, int64_t stride, hipMemcpyKind kind, hipStream_t st)
+{
+    const size_t count = item_count(n, stride);
+    const bool up = kind == hipMemcpyHostToDevice;
+    void *dst = up ? dev : const_cast<void *>(host);
+    const void *src = up ? host : dev;
+    if (bytes == 0) return 0;
+    if (count == 1 || stride == (int64_t)bytes)
+        TMF_HIP(hipMemcpyAsync(dst, src, bytes * count, kind, st));
+    else
+        TMF_HIP(hipMemcpy2DAsync(dst, up ? bytes : (size_t)stride, src, up ? (size_t)stride : bytes, bytes, count, kind, st));
+    return 0;
+}
+
+// Host tiles (tile_stride apart; 0: one tile) staged into `buf`; *dstride is the stride the
+// kernels then use.
 int stage_tiles(const uint8_t *tiles, int64_t n, int64_t tile_stride, size_t tbytes, hipStream_t st, DevBuf &buf, const uint8_t **dev,
                 int64_t *dstride)
 {
-    const size_t nt = tile_stride ? (size_t)n : 1;
-    if (int rc = buf.alloc(tbytes * nt, st, "watermark tiles")) return rc;
-    if (tbytes) {
-        if (nt == 1 || tile_stride == (int64_t)tbytes)
-            TMF_HIP(hipMemcpyAsync(buf.p, tiles, tbytes * nt, hipMemcpyHostToDevice, st));
-        else
-            TMF_HIP(hipMemcpy2DAsync(buf.p, tbytes, tiles, (size_t)tile_stride, tbytes, nt, hipMemcpyHostToDevice, st));
-    }
+    if (int rc = buf.alloc(tbytes * item_count(n, tile_stride), st, "watermark tiles")) return rc;
+    if (int rc = copy_items(buf.p, tiles, tbytes, n, tile_stride, hipMemcpyHostToDevice, st)) return rc;
     *dev = static_cast<const uint8_t *>(buf.p);
     *dstride = tile_stride ? (int64_t)tbytes : 0;
     return 0;
@@ -208,9 +220,18 @@ int64_t list_cap()
 }
 
 struct Chunks {
-    int64_t per_frame = 0, frames = 0, n = 0, cap = 0;
+    int64_t per_frame = 0, frames = 0, n = 0, cap = 0, total = 0;
+    int64_t first(int64_t c) const { return c * frames; }  // chunk c: frames [first, first + count)
+    int64_t count(int64_t c) const { return std::min(frames, total - c * frames); }
+    std::vector<int64_t> blocks() const  // per chunk, for two_pass
+    {
+        std::vector<int64_t> b((size_t)n);
+        for (int64_t c = 0; c < n; ++c) b[(size_t)c] = count(c) * per_frame;
+        return b;
+    }
     void plan(int64_t nframes, int64_t blocks_per_frame)
     {
+        total = nframes;
         per_frame = blocks_per_frame;
         frames = blocks_per_frame > 0 ? list_cap() / blocks_per_frame : nframes;
         if (frames < 1) frames = 1;
@@ -291,6 +312,122 @@ struct HostSink {
     HostSink &operator=(const HostSink &) = delete;
 };
 
+// ---- the two-pass driver: the bookkeeping above, once, for every batch call
+
+// The lists and counters of one chunk, under the names the kernels' argument structs give them.
+struct ChunkLists {
+    uint32_t *fb_list, *fb_count, *fb_bad;           // dgesdd route: ids, how many, how many did not converge
+    uint32_t *slow_list, *slow_count, *slow_shards;  // list pass (list and shards null: the call has none)
+};
+
+template <class Args>  // EmbedArgs, ExtractArgs, KeyedArgs: the same six fields
+void wire_lists(Args &k, const ChunkLists &w)
+{
+    k.fb_list = w.fb_list;
+    k.fb_count = w.fb_count;
+    k.fb_bad = w.fb_bad;
+    k.slow_list = w.slow_list;
+    k.slow_count = w.slow_count;
+    k.slow_shards = w.slow_shards;
+}
+
+// Where a call's per-chunk counts (dgesdd-route blocks, dbdsqr non-convergence, list-pass blocks)
+// go.  They are read back -- which synchronises the stream -- when the caller asks for the count
+// (n_lapack) or when `check` is set (the host-memory calls, which synchronise anyway): a dbdsqr
+// that did not converge then fails the call (np.linalg.svd raises LinAlgError there).  With a
+// `sink` they are copied there on the stream instead and nothing synchronises here: whoever owns
+// the sink sums it after its own synchronisation (HostCall, tmf::embed_device_async).  An
+// asynchronous device-memory call without a count pointer is not checked (include/tmfwm.h).
+struct Report {
+    int64_t *n_lapack;
+    bool check;
+    uint32_t *sink;
+};
+
+// Both passes of a call whose chunks hold blocks[c] blocks each.  enqueue(c, lists) launches
+// chunk c's first pass (or launch_list_all) and then its fixup pass on `st`, with `lists` wired
+// into its argument struct; here, around it: the allocations, the zeroed counts, the reset of the
+// segment counters before each chunk, the TMFWM_DEBUG_FORCE_NONCONV poke after it (chunks with
+// a block only) and the report.
+//   list_pass    allocate the list-pass list and its segment counters (else the kernels get null)
+//   edge_chunks  ragged: a chunk may hold edge pixels and no block, and is enqueued all the same;
+//                without it a call with no block anywhere reports zero counts at once and
+//                allocates nothing
+template <class Enqueue>
+int two_pass(const std::vector<int64_t> &blocks, bool list_pass, bool edge_chunks, hipStream_t st, const Report &rep, Enqueue enqueue)
+{
+    const int64_t nch = (int64_t)blocks.size();
+    const int64_t cap = nch ? *std::max_element(blocks.begin(), blocks.end()) : 0;  // ids are relative to the chunk
+    if (cap == 0 && !edge_chunks) {
+        if (rep.sink) std::fill(rep.sink, rep.sink + 3 * nch, 0u);
+        if (rep.n_lapack) {
+            *rep.n_lapack = 0;
+            t_list_pass = 0;
+        }
+        return 0;
+    }
+    DevBuf list, slow, shards, counts;
+    const size_t shard_bytes = (size_t)tmf::kListShards * tmf::kShardStride * 4;
+    if (int rc = list.alloc((size_t)cap * 4, st, "dgesdd-route block list")) return rc;
+    if (list_pass) {
+        if (int rc = slow.alloc((size_t)cap * 4, st, "list-pass block list")) return rc;
+        if (int rc = shards.alloc(shard_bytes, st, "list-pass segment counters")) return rc;
+    }
+    // per chunk: dgesdd-route count, non-convergence count, list-pass count
+    if (int rc = counts.alloc((size_t)nch * 12, st, "block-list counts")) return rc;
+    TMF_HIP(hipMemsetAsync(counts.p, 0, (size_t)nch * 12, st));
+    uint32_t *const cnt = static_cast<uint32_t *>(counts.p);
+    for (int64_t c = 0; c < nch; ++c) {
+        const ChunkLists w{static_cast<uint32_t *>(list.p), cnt + c,           cnt + nch + c,
+                           static_cast<uint32_t *>(slow.p), cnt + 2 * nch + c, static_cast<uint32_t *>(shards.p)};
+        if (shards.p) TMF_HIP(hipMemsetAsync(shards.p, 0, shard_bytes, st));
+        if (int rc = enqueue(c, w)) return rc;
+        if (blocks[(size_t)c] > 0 && force_nonconv()) TMF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w.fb_bad), 1, 1, st));
+    }
+    if (rep.sink) {
+        TMF_HIP(hipMemcpyAsync(rep.sink, counts.p, (size_t)nch * 12, hipMemcpyDeviceToHost, st));
+        return 0;
+    }
+    if (rep.n_lapack || rep.check) return sum_counts(cnt, nch, st, rep.n_lapack);
+    return 0;
+}
+
+// ---- the call shell of the batch entry points
+
+// Every batch entry point starts here.  A route outside the enumeration leaves *n_lapack as the
+// caller had it; from the zeroing on, an early return leaves this call's counts at 0.
+int begin_call(int32_t route, int64_t *n_lapack, bool rank1_routes = true)
+{
+    t_err.clear();
+    if (route < TMFWM_ROUTE_HYBRID || route > TMFWM_ROUTE_RANK1_REFERENCE) return fail(TMFWM_ERR_INVALID, "route %d", route);
+    if (!rank1_routes && (route == TMFWM_ROUTE_RANK1 || route == TMFWM_ROUTE_RANK1_REFERENCE))
+        return fail(TMFWM_ERR_UNSUPPORTED, "the ragged calls do not take the rank-1 routes yet (route %d)", route);
+    if (n_lapack) {
+        *n_lapack = 0;
+        t_list_pass = 0;
+    }
+    return 0;
+}
+
+// The frame of a host-memory call, made once its inputs are staged: it takes a sink, the passes
+// run with report() -- their counts go to the sink; without one (more than kSinkChunks chunks)
+// they read the counts back themselves -- the caller enqueues the copies of its results, and
+// finish() synchronises the one time and sums the sink.
+struct HostCall {
+    HostSink sink;
+    int64_t nchunks, *n_lapack;
+    HostCall(int64_t nch, hipStream_t st, int64_t *n) : sink(nch, st), nchunks(nch), n_lapack(n) {}
+    Report report() const { return {n_lapack, true, sink.p}; }
+    int finish()
+    {
+        TMF_HIP(hipStreamSynchronize(sink.st));
+        return sink.p && nchunks ? tmf::sum_sink(sink.p, nchunks, n_lapack) : 0;
+    }
+};
+
+// a device-memory call has no sink: it reads the counts back if the caller gave a count pointer
+Report device_report(int64_t *n_lapack) { return {n_lapack, false, nullptr}; }
+
 }  // namespace
 
 namespace tmf {
@@ -309,215 +446,117 @@ void clear_error() { t_err.clear(); }
 
 int check_frames(int64_t n, int32_t H, int32_t W, int64_t stride, int32_t block) { return ::check_frames(n, H, W, stride, block); }
 
-// Both passes of embed over device-resident frames (a.src / a.dst / a.wm set).  The
-// per-chunk counts (dgesdd-route blocks, dbdsqr non-convergence, list-pass blocks) are read
-// back -- which synchronises the stream -- when the caller asks for the count (n_lapack) or
-// when `check` is set (the host-memory calls, which synchronise anyway): a dbdsqr that did not
-// converge then fails the call (np.linalg.svd raises LinAlgError there).  An asynchronous
-// device-memory call without a count pointer is not checked (include/tmfwm.h).
-int run_embed(EmbedArgs a, hipStream_t st, int64_t *n_lapack, bool check, uint32_t *sink = nullptr, int route = TMFWM_ROUTE_HYBRID)
+// Both passes of embed over device-resident frames (a.src / a.dst / a.wm set).
+int run_embed(const EmbedArgs &a, hipStream_t st, const Report &rep, int route)
 {
     Chunks ch;
     ch.plan(a.nframes, (int64_t)a.nbh * a.nbw);
-    DevBuf list, slow, shards, counts;
-    if (ch.cap > 0) {
-        if (int rc = list.alloc((size_t)ch.cap * 4, st, "dgesdd-route block list")) return rc;
-        if ((embed_defers(a.block) && route != TMFWM_ROUTE_REFERENCE && route != TMFWM_ROUTE_RANK1_REFERENCE) ||
-            (route == TMFWM_ROUTE_RANK1 && rank1_block(a.block))) {
-            if (int rc = slow.alloc((size_t)ch.cap * 4, st, "list-pass block list")) return rc;
-            if (int rc = shards.alloc((size_t)kListShards * kShardStride * 4, st, "list-pass segment counters")) return rc;
-        }
-        // per chunk: dgesdd-route count, non-convergence count, list-pass count
-        if (int rc = counts.alloc((size_t)ch.n * 12, st, "block-list counts")) return rc;
-        TMF_HIP(hipMemsetAsync(counts.p, 0, (size_t)ch.n * 12, st));
-    }
-    if (ch.cap == 0) {  // no full block: colour round trip only
-        TMF_HIP(launch_embed(a, st));
-        if (sink) std::fill(sink, sink + 3 * ch.n, 0u);
-        if (n_lapack) {
-            *n_lapack = 0;
-            t_list_pass = 0;
-        }
-        return 0;
-    }
-    for (int64_t c = 0; c < ch.n; ++c) {
+    if (ch.cap == 0) TMF_HIP(launch_embed(a, st));  // no full block: the colour round trip only, zero counts
+    const bool pre = (route == TMFWM_ROUTE_RANK1 || route == TMFWM_ROUTE_RANK1_REFERENCE) && rank1_block(a.block);
+    const bool list_pass = (embed_defers(a.block) && route != TMFWM_ROUTE_REFERENCE && route != TMFWM_ROUTE_RANK1_REFERENCE) ||
+                           (route == TMFWM_ROUTE_RANK1 && pre);
+    return two_pass(ch.blocks(), list_pass, false, st, rep, [&](int64_t c, const ChunkLists &w) -> int {
         EmbedArgs k = a;
-        const int64_t f0 = c * ch.frames;
-        k.nframes = a.nframes - f0 < ch.frames ? a.nframes - f0 : ch.frames;
+        const int64_t f0 = ch.first(c), nb = ch.count(c) * ch.per_frame;
+        k.nframes = ch.count(c);
         k.src = a.src + f0 * a.frame_stride;
         k.dst = a.dst + f0 * a.frame_stride;
         k.wm = a.wm + f0 * a.wm_stride;  // the lists' block ids are relative to the chunk: so is its first tile
-        k.fb_list = static_cast<uint32_t *>(list.p);
-        k.fb_count = static_cast<uint32_t *>(counts.p) + c;
-        k.fb_bad = static_cast<uint32_t *>(counts.p) + ch.n + c;
-        k.slow_list = static_cast<uint32_t *>(slow.p);  // null unless embed_defers(block)
-        k.slow_count = static_cast<uint32_t *>(counts.p) + 2 * ch.n + c;
-        k.slow_shards = static_cast<uint32_t *>(shards.p);
-        if (shards.p) TMF_HIP(hipMemsetAsync(shards.p, 0, (size_t)kListShards * kShardStride * 4, st));
-        const bool pre = (route == TMFWM_ROUTE_RANK1 || route == TMFWM_ROUTE_RANK1_REFERENCE) && rank1_block(k.block);
+        wire_lists(k, w);
         if (route == TMFWM_ROUTE_REFERENCE || (route == TMFWM_ROUTE_RANK1_REFERENCE && !pre)) {
             // every block on the dgesdd route; the edges as always
             TMF_HIP(launch_edges(k.src, k.dst, k.nframes, k.H, k.W, k.frame_stride, k.block, st));
-            TMF_HIP(launch_list_all(k.fb_list, k.fb_count, k.nframes * ch.per_frame, st));
+            TMF_HIP(launch_list_all(k.fb_list, k.fb_count, nb, st));
         } else if (pre) {  // the rank-1 pre-pass (+ its list pass for TMFWM_ROUTE_RANK1), the edges
             if (route == TMFWM_ROUTE_RANK1_REFERENCE) k.slow_list = nullptr;
             TMF_HIP(launch_embed_rank1(k, st));
         } else {
             TMF_HIP(launch_embed(k, st));
         }
-        TMF_HIP(launch_embed_fixup(k, k.fb_list, k.fb_count, k.nframes * ch.per_frame, st));
-        if (force_nonconv()) TMF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(k.fb_bad), 1, 1, st));
-    }
-    if (sink) {  // tmf::embed_device_async / extract_device_async: the caller sums after its sync
-        TMF_HIP(hipMemcpyAsync(sink, counts.p, (size_t)ch.n * 12, hipMemcpyDeviceToHost, st));
+        TMF_HIP(launch_embed_fixup(k, k.fb_list, k.fb_count, nb, st));
         return 0;
-    }
-    if (n_lapack || check) return sum_counts(static_cast<const uint32_t *>(counts.p), ch.n, st, n_lapack);
-    return 0;
+    });
 }
 
-int run_extract(ExtractArgs a, hipStream_t st, int64_t *n_lapack, bool check, uint32_t *sink = nullptr,
-                int route = TMFWM_ROUTE_HYBRID)
+int run_extract(const ExtractArgs &a, hipStream_t st, const Report &rep, int route)
 {
     Chunks ch;
     ch.plan(a.nframes, (int64_t)a.nbh * a.nbw);
-    if (ch.cap == 0) {
-        if (sink) std::fill(sink, sink + 3 * ch.n, 0u);
-        if (n_lapack) {
-            *n_lapack = 0;
-            t_list_pass = 0;
-        }
-        return 0;
-    }
-    DevBuf list, slow, shards, counts;
-    if (int rc = list.alloc((size_t)ch.cap * 4, st, "dgesdd-route block list")) return rc;
-    if (route != TMFWM_ROUTE_REFERENCE) {  // hybrid (TMFWM_ROUTE_RANK1: extract is the hybrid route)
-        if (int rc = slow.alloc((size_t)ch.cap * 4, st, "list-pass block list")) return rc;
-        if (int rc = shards.alloc((size_t)kListShards * kShardStride * 4, st, "list-pass segment counters")) return rc;
-    }
-    if (int rc = counts.alloc((size_t)ch.n * 12, st, "block-list counts")) return rc;  // as run_embed's
-    TMF_HIP(hipMemsetAsync(counts.p, 0, (size_t)ch.n * 12, st));
-    for (int64_t c = 0; c < ch.n; ++c) {
+    // the list pass on every route but the reference (TMFWM_ROUTE_RANK1: extract is the hybrid route)
+    return two_pass(ch.blocks(), route != TMFWM_ROUTE_REFERENCE, false, st, rep, [&](int64_t c, const ChunkLists &w) -> int {
         ExtractArgs k = a;
-        const int64_t f0 = c * ch.frames;
-        k.nframes = a.nframes - f0 < ch.frames ? a.nframes - f0 : ch.frames;
+        const int64_t f0 = ch.first(c), nb = ch.count(c) * ch.per_frame;
+        k.nframes = ch.count(c);
         k.wsrc = a.wsrc + f0 * a.frame_stride;
         k.osrc = a.osrc + f0 * a.frame_stride;
         k.out = a.out + f0 * a.tile_stride;
-        k.fb_list = static_cast<uint32_t *>(list.p);
-        k.fb_count = static_cast<uint32_t *>(counts.p) + c;
-        k.fb_bad = static_cast<uint32_t *>(counts.p) + ch.n + c;
-        k.slow_list = static_cast<uint32_t *>(slow.p);
-        k.slow_count = static_cast<uint32_t *>(counts.p) + 2 * ch.n + c;
-        k.slow_shards = static_cast<uint32_t *>(shards.p);
-        if (shards.p) TMF_HIP(hipMemsetAsync(shards.p, 0, (size_t)kListShards * kShardStride * 4, st));
-        if (route == TMFWM_ROUTE_REFERENCE) TMF_HIP(launch_list_all(k.fb_list, k.fb_count, k.nframes * ch.per_frame, st));
+        wire_lists(k, w);
+        if (route == TMFWM_ROUTE_REFERENCE) TMF_HIP(launch_list_all(k.fb_list, k.fb_count, nb, st));
         else TMF_HIP(launch_extract(k, st));
-        TMF_HIP(launch_extract_fixup(k, k.fb_list, k.fb_count, k.nframes * ch.per_frame, st));
-        if (force_nonconv()) TMF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(k.fb_bad), 1, 1, st));
-    }
-    if (sink) {  // tmf::embed_device_async / extract_device_async: the caller sums after its sync
-        TMF_HIP(hipMemcpyAsync(sink, counts.p, (size_t)ch.n * 12, hipMemcpyDeviceToHost, st));
+        TMF_HIP(launch_extract_fixup(k, k.fb_list, k.fb_count, nb, st));
         return 0;
-    }
-    if (n_lapack || check) return sum_counts(static_cast<const uint32_t *>(counts.p), ch.n, st, n_lapack);
-    return 0;
+    });
 }
 
 // Keyed extraction over device-resident frames (a.src, and a.key_out for the map or a.key / a.out
-// for the extract, set): run_extract's chunks, lists, counts and reporting, on one image per frame.
-int run_keyed(KeyedArgs a, bool map, hipStream_t st, int64_t *n_lapack, bool check, uint32_t *sink, int route)
+// for the extract, set): as run_extract, on one image per frame.
+int run_keyed(const KeyedArgs &a, bool map, hipStream_t st, const Report &rep, int route)
 {
     Chunks ch;
     ch.plan(a.nframes, (int64_t)a.nbh * a.nbw);
-    if (ch.cap == 0) {
-        if (sink) std::fill(sink, sink + 3 * ch.n, 0u);
-        if (n_lapack) {
-            *n_lapack = 0;
-            t_list_pass = 0;
-        }
-        return 0;
-    }
-    DevBuf list, slow, shards, counts;
-    if (int rc = list.alloc((size_t)ch.cap * 4, st, "dgesdd-route block list")) return rc;
-    if (route != TMFWM_ROUTE_REFERENCE) {  // the certified path, as extract's on every other route
-        if (int rc = slow.alloc((size_t)ch.cap * 4, st, "list-pass block list")) return rc;
-        if (int rc = shards.alloc((size_t)kListShards * kShardStride * 4, st, "list-pass segment counters")) return rc;
-    }
-    if (int rc = counts.alloc((size_t)ch.n * 12, st, "block-list counts")) return rc;  // as run_embed's
-    TMF_HIP(hipMemsetAsync(counts.p, 0, (size_t)ch.n * 12, st));
-    for (int64_t c = 0; c < ch.n; ++c) {
+    return two_pass(ch.blocks(), route != TMFWM_ROUTE_REFERENCE, false, st, rep, [&](int64_t c, const ChunkLists &w) -> int {
         KeyedArgs k = a;
-        const int64_t f0 = c * ch.frames;
-        k.nframes = a.nframes - f0 < ch.frames ? a.nframes - f0 : ch.frames;
+        const int64_t f0 = ch.first(c), nb = ch.count(c) * ch.per_frame;
+        k.nframes = ch.count(c);
         k.src = a.src + f0 * a.frame_stride;
         if (map) k.key_out = a.key_out + f0 * a.key_stride;
         else {
             k.key = a.key + f0 * a.key_stride;  // stride 0: the one shared key
             k.out = a.out + f0 * a.tile_stride;
         }
-        k.fb_list = static_cast<uint32_t *>(list.p);
-        k.fb_count = static_cast<uint32_t *>(counts.p) + c;
-        k.fb_bad = static_cast<uint32_t *>(counts.p) + ch.n + c;
-        k.slow_list = static_cast<uint32_t *>(slow.p);
-        k.slow_count = static_cast<uint32_t *>(counts.p) + 2 * ch.n + c;
-        k.slow_shards = static_cast<uint32_t *>(shards.p);
-        if (shards.p) TMF_HIP(hipMemsetAsync(shards.p, 0, (size_t)kListShards * kShardStride * 4, st));
-        if (route == TMFWM_ROUTE_REFERENCE) TMF_HIP(launch_list_all(k.fb_list, k.fb_count, k.nframes * ch.per_frame, st));
+        wire_lists(k, w);
+        if (route == TMFWM_ROUTE_REFERENCE) TMF_HIP(launch_list_all(k.fb_list, k.fb_count, nb, st));
         else TMF_HIP(map ? launch_sigma1_map(k, st) : launch_extract_keyed(k, st));
-        TMF_HIP(map ? launch_sigma1_fixup(k, k.fb_list, k.fb_count, k.nframes * ch.per_frame, st)
-                    : launch_extract_keyed_fixup(k, k.fb_list, k.fb_count, k.nframes * ch.per_frame, st));
-        if (force_nonconv()) TMF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(k.fb_bad), 1, 1, st));
-    }
-    if (sink) {
-        TMF_HIP(hipMemcpyAsync(sink, counts.p, (size_t)ch.n * 12, hipMemcpyDeviceToHost, st));
+        TMF_HIP(map ? launch_sigma1_fixup(k, k.fb_list, k.fb_count, nb, st) : launch_extract_keyed_fixup(k, k.fb_list, k.fb_count, nb, st));
         return 0;
-    }
-    if (n_lapack || check) return sum_counts(static_cast<const uint32_t *>(counts.p), ch.n, st, n_lapack);
-    return 0;
+    });
 }
 
-KeyedArgs keyed_args(int64_t n, int32_t H, int32_t W, int64_t stride, int32_t block, double alpha)
+// the geometry every launch struct carries
+template <class Args>
+Args geometry(int64_t n, int32_t H, int32_t W, int64_t stride, int32_t block)
 {
-    KeyedArgs a{};
+    Args a{};
     a.nframes = n;
     a.frame_stride = stride;
-    a.tile_stride = (int64_t)(H / block) * (W / block);
-    a.key_stride = a.tile_stride;
     a.H = H;
     a.W = W;
     a.block = block;
     a.nbh = H / block;
     a.nbw = W / block;
-    a.alpha32 = (float)alpha;
     return a;
 }
 
 EmbedArgs embed_args(int64_t n, int32_t H, int32_t W, int64_t stride, int32_t block, double alpha)
 {
-    EmbedArgs a{};
-    a.nframes = n;
-    a.frame_stride = stride;
-    a.H = H;
-    a.W = W;
-    a.block = block;
-    a.nbh = H / block;
-    a.nbw = W / block;
+    EmbedArgs a = geometry<EmbedArgs>(n, H, W, stride, block);
     a.alpha = alpha;
     return a;
 }
 
 ExtractArgs extract_args(int64_t n, int32_t H, int32_t W, int64_t stride, int32_t block, double alpha)
 {
-    ExtractArgs a{};
-    a.nframes = n;
-    a.frame_stride = stride;
-    a.tile_stride = (int64_t)(H / block) * (W / block);
-    a.H = H;
-    a.W = W;
-    a.block = block;
-    a.nbh = H / block;
-    a.nbw = W / block;
+    ExtractArgs a = geometry<ExtractArgs>(n, H, W, stride, block);
+    a.tile_stride = (int64_t)a.nbh * a.nbw;
+    a.alpha32 = (float)alpha;
+    return a;
+}
+
+KeyedArgs keyed_args(int64_t n, int32_t H, int32_t W, int64_t stride, int32_t block, double alpha)
+{
+    KeyedArgs a = geometry<KeyedArgs>(n, H, W, stride, block);
+    a.tile_stride = (int64_t)a.nbh * a.nbw;
+    a.key_stride = a.tile_stride;
     a.alpha32 = (float)alpha;
     return a;
 }
@@ -548,7 +587,7 @@ int embed_device_async(const uint8_t *src, int64_t n, int H, int W, int64_t stri
     a.wm = tile;
     a.wm_stride = tile_stride;
     a.aligned = dev_aligned(src, dst, stride, W);
-    return run_embed(a, st, nullptr, false, sink, route);
+    return run_embed(a, st, Report{nullptr, false, sink}, route);
 }
 
 int extract_device_async(const uint8_t *wsrc, const uint8_t *osrc, int64_t n, int H, int W, int64_t stride, int block,
@@ -564,7 +603,7 @@ int extract_device_async(const uint8_t *wsrc, const uint8_t *osrc, int64_t n, in
     a.osrc = osrc;
     a.out = out;
     a.aligned = dev_aligned(wsrc, osrc, stride, W);
-    return run_extract(a, st, nullptr, false, sink, route);
+    return run_extract(a, st, Report{nullptr, false, sink}, route);
 }
 
 int sum_sink(const uint32_t *sink, int64_t nchunks, int64_t *lapack) { return sum_host_counts(sink, nchunks, lapack); }
@@ -596,12 +635,7 @@ static int embed_rgb(const uint8_t *rgb, int64_t n_frames, int32_t height, int32
                      const uint8_t *wm_tile, int64_t tile_stride, int32_t block, double alpha, uint8_t *out, int32_t mem_kind,
                      void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
 {
-    t_err.clear();
-    if (route < TMFWM_ROUTE_HYBRID || route > TMFWM_ROUTE_RANK1_REFERENCE) return fail(TMFWM_ERR_INVALID, "route %d", route);
-    if (n_lapack_blocks) {
-        *n_lapack_blocks = 0;
-        t_list_pass = 0;  // this call's count from here on (an early return leaves 0)
-    }
+    if (int rc = begin_call(route, n_lapack_blocks)) return rc;
     if (int rc = check_frames(n_frames, height, width, frame_stride, block)) return rc;
     const int nbh = height / block, nbw = width / block;
     if (int rc = check_tile_stride(tile_stride, (int64_t)nbh * nbw)) return rc;
@@ -626,7 +660,7 @@ static int embed_rgb(const uint8_t *rgb, int64_t n_frames, int32_t height, int32
         a.wm = wm_tile;
         a.wm_stride = tile_stride;
         a.aligned = tmf::dev_aligned(rgb, out, frame_stride, width);
-        return tmf::run_embed(a, st, n_lapack_blocks, false, nullptr, route);
+        return tmf::run_embed(a, st, device_report(n_lapack_blocks), route);
     }
     if (mem_kind != TMFWM_MEM_HOST) return fail(TMFWM_ERR_INVALID, "mem_kind %d", mem_kind);
     if (!rgb || !out || (tbytes && !wm_tile)) return fail(TMFWM_ERR_INVALID, "NULL host pointer");
@@ -638,9 +672,8 @@ static int embed_rgb(const uint8_t *rgb, int64_t n_frames, int32_t height, int32
     a.src = static_cast<const uint8_t *>(din.p);
     a.dst = static_cast<uint8_t *>(dout.p);
     a.aligned = frame_stride % 4 == 0 && width % 4 == 0;
-    const int64_t nch = tmf::count_chunks(n_frames, height, width, block);
-    HostSink sink(nch, st);
-    if (int rc = tmf::run_embed(a, st, n_lapack_blocks, true, sink.p, route)) return rc;
+    HostCall hc(tmf::count_chunks(n_frames, height, width, block), st, n_lapack_blocks);
+    if (int rc = tmf::run_embed(a, st, hc.report(), route)) return rc;
     if (frame_stride == fbytes) {
         TMF_HIP(hipMemcpyAsync(out, dout.p, span, hipMemcpyDeviceToHost, st));
     } else {
@@ -648,8 +681,7 @@ static int embed_rgb(const uint8_t *rgb, int64_t n_frames, int32_t height, int32
             TMF_HIP(hipMemcpyAsync(out + f * frame_stride, static_cast<uint8_t *>(dout.p) + f * frame_stride, (size_t)fbytes,
                                    hipMemcpyDeviceToHost, st));
     }
-    TMF_HIP(hipStreamSynchronize(st));
-    return sink.p ? tmf::sum_sink(sink.p, nch, n_lapack_blocks) : 0;
+    return hc.finish();
 }
 
 int tmfwm_embed_route(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
@@ -678,12 +710,7 @@ int tmfwm_extract_route(const uint8_t *wm_rgb, const uint8_t *orig_rgb, int64_t 
                         int64_t frame_stride, int32_t block, double alpha, uint8_t *out_tiles, int32_t mem_kind,
                         void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
 {
-    t_err.clear();
-    if (route < TMFWM_ROUTE_HYBRID || route > TMFWM_ROUTE_RANK1_REFERENCE) return fail(TMFWM_ERR_INVALID, "route %d", route);
-    if (n_lapack_blocks) {
-        *n_lapack_blocks = 0;
-        t_list_pass = 0;  // this call's count from here on (an early return leaves 0)
-    }
+    if (int rc = begin_call(route, n_lapack_blocks)) return rc;
     if (int rc = check_frames(n_frames, height, width, frame_stride, block)) return rc;
     if (!std::isfinite(alpha) || alpha == 0.0) return fail(TMFWM_ERR_INVALID, "alpha must be finite and non-zero");
     if (int rc = need_device()) return rc;
@@ -705,7 +732,7 @@ int tmfwm_extract_route(const uint8_t *wm_rgb, const uint8_t *orig_rgb, int64_t 
         a.osrc = orig_rgb;
         a.out = out_tiles;
         a.aligned = tmf::dev_aligned(wm_rgb, orig_rgb, frame_stride, width);
-        return tmf::run_extract(a, st, n_lapack_blocks, false, nullptr, route);
+        return tmf::run_extract(a, st, device_report(n_lapack_blocks), route);
     }
     if (mem_kind != TMFWM_MEM_HOST) return fail(TMFWM_ERR_INVALID, "mem_kind %d", mem_kind);
     if (!wm_rgb || !orig_rgb || !out_tiles) return fail(TMFWM_ERR_INVALID, "NULL host pointer");
@@ -719,12 +746,10 @@ int tmfwm_extract_route(const uint8_t *wm_rgb, const uint8_t *orig_rgb, int64_t 
     a.osrc = static_cast<const uint8_t *>(dor.p);
     a.out = static_cast<uint8_t *>(dout.p);
     a.aligned = frame_stride % 4 == 0 && width % 4 == 0;
-    const int64_t nch = tmf::count_chunks(n_frames, height, width, block);
-    HostSink sink(nch, st);
-    if (int rc = tmf::run_extract(a, st, n_lapack_blocks, true, sink.p, route)) return rc;
+    HostCall hc(tmf::count_chunks(n_frames, height, width, block), st, n_lapack_blocks);
+    if (int rc = tmf::run_extract(a, st, hc.report(), route)) return rc;
     TMF_HIP(hipMemcpyAsync(out_tiles, dout.p, (size_t)(tbytes * n_frames), hipMemcpyDeviceToHost, st));
-    TMF_HIP(hipStreamSynchronize(st));
-    return sink.p ? tmf::sum_sink(sink.p, nch, n_lapack_blocks) : 0;
+    return hc.finish();
 }
 
 int tmfwm_extract_ex(const uint8_t *wm_rgb, const uint8_t *orig_rgb, int64_t n_frames, int32_t height, int32_t width,
@@ -746,12 +771,7 @@ int tmfwm_extract(const uint8_t *wm_rgb, const uint8_t *orig_rgb, int64_t n_fram
 int tmfwm_sigma1_map(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride, int32_t block,
                      float *out_key, int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
 {
-    t_err.clear();
-    if (route < TMFWM_ROUTE_HYBRID || route > TMFWM_ROUTE_RANK1_REFERENCE) return fail(TMFWM_ERR_INVALID, "route %d", route);
-    if (n_lapack_blocks) {
-        *n_lapack_blocks = 0;
-        t_list_pass = 0;
-    }
+    if (int rc = begin_call(route, n_lapack_blocks)) return rc;
     if (int rc = check_frames(n_frames, height, width, frame_stride, block)) return rc;
     if (int rc = need_device()) return rc;
     const int64_t kbytes = (int64_t)(height / block) * (width / block) * 4;
@@ -767,7 +787,7 @@ int tmfwm_sigma1_map(const uint8_t *rgb, int64_t n_frames, int32_t height, int32
         a.src = rgb;
         a.key_out = out_key;
         a.aligned = tmf::dev_aligned(rgb, rgb, frame_stride, width);
-        return tmf::run_keyed(a, true, st, n_lapack_blocks, false, nullptr, route);
+        return tmf::run_keyed(a, true, st, device_report(n_lapack_blocks), route);
     }
     if (mem_kind != TMFWM_MEM_HOST) return fail(TMFWM_ERR_INVALID, "mem_kind %d", mem_kind);
     if (!rgb || !out_key) return fail(TMFWM_ERR_INVALID, "NULL host pointer");
@@ -778,24 +798,17 @@ int tmfwm_sigma1_map(const uint8_t *rgb, int64_t n_frames, int32_t height, int32
     a.src = static_cast<const uint8_t *>(din.p);
     a.key_out = static_cast<float *>(dkey.p);
     a.aligned = frame_stride % 4 == 0 && width % 4 == 0;
-    const int64_t nch = tmf::count_chunks(n_frames, height, width, block);
-    HostSink sink(nch, st);
-    if (int rc = tmf::run_keyed(a, true, st, n_lapack_blocks, true, sink.p, route)) return rc;
+    HostCall hc(tmf::count_chunks(n_frames, height, width, block), st, n_lapack_blocks);
+    if (int rc = tmf::run_keyed(a, true, st, hc.report(), route)) return rc;
     TMF_HIP(hipMemcpyAsync(out_key, dkey.p, obytes, hipMemcpyDeviceToHost, st));
-    TMF_HIP(hipStreamSynchronize(st));
-    return sink.p ? tmf::sum_sink(sink.p, nch, n_lapack_blocks) : 0;
+    return hc.finish();
 }
 
 int tmfwm_extract_keyed(const uint8_t *wm_rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
                         const float *key, int64_t key_stride, int32_t block, double alpha, uint8_t *out_tiles, int32_t mem_kind,
                         void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
 {
-    t_err.clear();
-    if (route < TMFWM_ROUTE_HYBRID || route > TMFWM_ROUTE_RANK1_REFERENCE) return fail(TMFWM_ERR_INVALID, "route %d", route);
-    if (n_lapack_blocks) {
-        *n_lapack_blocks = 0;
-        t_list_pass = 0;
-    }
+    if (int rc = begin_call(route, n_lapack_blocks)) return rc;
     if (int rc = check_frames(n_frames, height, width, frame_stride, block)) return rc;
     if (!std::isfinite(alpha) || alpha == 0.0) return fail(TMFWM_ERR_INVALID, "alpha must be finite and non-zero");
     const int64_t tbytes = (int64_t)(height / block) * (width / block), kbytes = tbytes * 4;
@@ -820,29 +833,25 @@ int tmfwm_extract_keyed(const uint8_t *wm_rgb, int64_t n_frames, int32_t height,
         a.key_stride = key_stride / 4;
         a.out = out_tiles;
         a.aligned = tmf::dev_aligned(wm_rgb, wm_rgb, frame_stride, width);
-        return tmf::run_keyed(a, false, st, n_lapack_blocks, false, nullptr, route);
+        return tmf::run_keyed(a, false, st, device_report(n_lapack_blocks), route);
     }
     if (mem_kind != TMFWM_MEM_HOST) return fail(TMFWM_ERR_INVALID, "mem_kind %d", mem_kind);
     if (!wm_rgb || !key || !out_tiles) return fail(TMFWM_ERR_INVALID, "NULL host pointer");
     DevBuf dw, dkey, dout;
-    const size_t nk = key_stride ? (size_t)n_frames : 1;  // staged compact
     if (int rc = dw.alloc(span, st, "watermarked frames")) return rc;
-    if (int rc = dkey.alloc((size_t)kbytes * nk, st, "sigma_1 key maps")) return rc;
+    if (int rc = dkey.alloc((size_t)kbytes * item_count(n_frames, key_stride), st, "sigma_1 key maps")) return rc;  // staged compact
     if (int rc = dout.alloc(obytes, st, "extracted tiles")) return rc;
     TMF_HIP(hipMemcpyAsync(dw.p, wm_rgb, span, hipMemcpyHostToDevice, st));
-    if (nk == 1 || key_stride == kbytes) TMF_HIP(hipMemcpyAsync(dkey.p, key, (size_t)kbytes * nk, hipMemcpyHostToDevice, st));
-    else TMF_HIP(hipMemcpy2DAsync(dkey.p, (size_t)kbytes, key, (size_t)key_stride, (size_t)kbytes, nk, hipMemcpyHostToDevice, st));
+    if (int rc = copy_items(dkey.p, key, (size_t)kbytes, n_frames, key_stride, hipMemcpyHostToDevice, st)) return rc;
     a.src = static_cast<const uint8_t *>(dw.p);
     a.key = static_cast<const float *>(dkey.p);
     a.key_stride = key_stride ? tbytes : 0;
     a.out = static_cast<uint8_t *>(dout.p);
     a.aligned = frame_stride % 4 == 0 && width % 4 == 0;
-    const int64_t nch = tmf::count_chunks(n_frames, height, width, block);
-    HostSink sink(nch, st);
-    if (int rc = tmf::run_keyed(a, false, st, n_lapack_blocks, true, sink.p, route)) return rc;
+    HostCall hc(tmf::count_chunks(n_frames, height, width, block), st, n_lapack_blocks);
+    if (int rc = tmf::run_keyed(a, false, st, hc.report(), route)) return rc;
     TMF_HIP(hipMemcpyAsync(out_tiles, dout.p, obytes, hipMemcpyDeviceToHost, st));
-    TMF_HIP(hipStreamSynchronize(st));
-    return sink.p ? tmf::sum_sink(sink.p, nch, n_lapack_blocks) : 0;
+    return hc.finish();
 }
 
 // ---- 4-byte pixels (ABI 8): the core runs on compact RGB device buffers; RGBX inputs are
@@ -898,11 +907,7 @@ int tmfwm_embed_tiles(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_fra
         return embed_rgb(rgb, n_frames, height, width, in_frame_stride, wm_tile, tile_stride, block, alpha, out, mem_kind, hip_stream,
                          route, n_lapack_blocks);
     }
-    if (route < TMFWM_ROUTE_HYBRID || route > TMFWM_ROUTE_RANK1_REFERENCE) return fail(TMFWM_ERR_INVALID, "route %d", route);
-    if (n_lapack_blocks) {
-        *n_lapack_blocks = 0;
-        t_list_pass = 0;
-    }
+    if (int rc = begin_call(route, n_lapack_blocks)) return rc;
     if (int rc = check_frames(n_frames, height, width, (int64_t)height * width * 3, block)) return rc;
     if (int rc = check_px(in_pixel_bytes, in_frame_stride, height, width, "input")) return rc;
     if (int rc = check_px(out_pixel_bytes, out_frame_stride, height, width, "output")) return rc;
@@ -947,29 +952,29 @@ int tmfwm_embed_tiles(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_fra
     a.wm = wm;
     a.wm_stride = wm_stride;
     a.aligned = tmf::dev_aligned(a.src, a.dst, s3, width);
-    const int64_t nch = tmf::count_chunks(n_frames, height, width, block);
-    HostSink sink(mem_kind == TMFWM_MEM_HOST ? nch : kSinkChunks + 1, st);
-    if (int rc = tmf::run_embed(a, st, n_lapack_blocks, mem_kind == TMFWM_MEM_HOST, sink.p, route)) return rc;
-    uint8_t *o = out;  // device destination of the output's final layout
-    if (mem_kind == TMFWM_MEM_HOST) {
-        if (int rc = dst4.alloc(ospan, st, "output staging")) return rc;
-        o = static_cast<uint8_t *>(dst4.p);
-    }
-    if (out_pixel_bytes == TMFWM_PIX_RGBX)
-        TMF_HIP(tmf::launch_unpack_rgbx(a.dst, s3, o, out_frame_stride, n_frames, height, width, st));
-    else
-        TMF_HIP(hipMemcpy2DAsync(o, (size_t)out_frame_stride, a.dst, (size_t)s3, (size_t)f3, (size_t)n_frames,
-                                 hipMemcpyDeviceToDevice, st));
-    if (mem_kind == TMFWM_MEM_HOST) {  // the caller's bytes between frames stay as they are
-        if (n_frames == 1 || out_frame_stride == fo)
-            TMF_HIP(hipMemcpyAsync(out, o, ospan, hipMemcpyDeviceToHost, st));
+    // the output's final layout (RGB or RGBX, the caller's stride) is made on the device, at `o`
+    auto layout = [&](uint8_t *o) -> int {
+        if (out_pixel_bytes == TMFWM_PIX_RGBX)
+            TMF_HIP(tmf::launch_unpack_rgbx(a.dst, s3, o, out_frame_stride, n_frames, height, width, st));
         else
-            TMF_HIP(hipMemcpy2DAsync(out, (size_t)out_frame_stride, o, (size_t)out_frame_stride, (size_t)fo, (size_t)n_frames,
-                                     hipMemcpyDeviceToHost, st));
-        TMF_HIP(hipStreamSynchronize(st));
-        if (sink.p) return tmf::sum_sink(sink.p, nch, n_lapack_blocks);
+            TMF_HIP(hipMemcpy2DAsync(o, (size_t)out_frame_stride, a.dst, (size_t)s3, (size_t)f3, (size_t)n_frames,
+                                     hipMemcpyDeviceToDevice, st));
+        return 0;
+    };
+    if (mem_kind == TMFWM_MEM_DEVICE) {
+        if (int rc = tmf::run_embed(a, st, device_report(n_lapack_blocks), route)) return rc;
+        return layout(out);
     }
-    return 0;
+    HostCall hc(tmf::count_chunks(n_frames, height, width, block), st, n_lapack_blocks);
+    if (int rc = tmf::run_embed(a, st, hc.report(), route)) return rc;
+    if (int rc = dst4.alloc(ospan, st, "output staging")) return rc;
+    if (int rc = layout(static_cast<uint8_t *>(dst4.p))) return rc;
+    if (n_frames == 1 || out_frame_stride == fo)  // the caller's bytes between frames stay as they are
+        TMF_HIP(hipMemcpyAsync(out, dst4.p, ospan, hipMemcpyDeviceToHost, st));
+    else
+        TMF_HIP(hipMemcpy2DAsync(out, (size_t)out_frame_stride, dst4.p, (size_t)out_frame_stride, (size_t)fo, (size_t)n_frames,
+                                 hipMemcpyDeviceToHost, st));
+    return hc.finish();
 }
 
 int tmfwm_embed_px(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_frame_stride, int64_t n_frames, int32_t height,
@@ -989,11 +994,7 @@ int tmfwm_extract_px(const uint8_t *wm_rgb, int32_t wm_pixel_bytes, int64_t wm_f
     if (wm_pixel_bytes == TMFWM_PIX_RGB && orig_pixel_bytes == TMFWM_PIX_RGB && wm_frame_stride == orig_frame_stride)
         return tmfwm_extract_route(wm_rgb, orig_rgb, n_frames, height, width, wm_frame_stride, block, alpha, out_tiles, mem_kind,
                                    hip_stream, route, n_lapack_blocks);
-    if (route < TMFWM_ROUTE_HYBRID || route > TMFWM_ROUTE_RANK1_REFERENCE) return fail(TMFWM_ERR_INVALID, "route %d", route);
-    if (n_lapack_blocks) {
-        *n_lapack_blocks = 0;
-        t_list_pass = 0;
-    }
+    if (int rc = begin_call(route, n_lapack_blocks)) return rc;
     if (int rc = check_frames(n_frames, height, width, (int64_t)height * width * 3, block)) return rc;
     if (int rc = check_px(wm_pixel_bytes, wm_frame_stride, height, width, "watermarked")) return rc;
     if (int rc = check_px(orig_pixel_bytes, orig_frame_stride, height, width, "original")) return rc;
@@ -1043,15 +1044,11 @@ int tmfwm_extract_px(const uint8_t *wm_rgb, int32_t wm_pixel_bytes, int64_t wm_f
         a.out = out_tiles;
     }
     a.aligned = tmf::dev_aligned(wp, op, f3, width);
-    const int64_t nch = tmf::count_chunks(n_frames, height, width, block);
-    HostSink sink(mem_kind == TMFWM_MEM_HOST ? nch : kSinkChunks + 1, st);
-    if (int rc = tmf::run_extract(a, st, n_lapack_blocks, mem_kind == TMFWM_MEM_HOST, sink.p, route)) return rc;
-    if (mem_kind == TMFWM_MEM_HOST) {
-        TMF_HIP(hipMemcpyAsync(out_tiles, dout.p, obytes, hipMemcpyDeviceToHost, st));
-        TMF_HIP(hipStreamSynchronize(st));
-        if (sink.p) return tmf::sum_sink(sink.p, nch, n_lapack_blocks);
-    }
-    return 0;
+    if (mem_kind == TMFWM_MEM_DEVICE) return tmf::run_extract(a, st, device_report(n_lapack_blocks), route);
+    HostCall hc(tmf::count_chunks(n_frames, height, width, block), st, n_lapack_blocks);
+    if (int rc = tmf::run_extract(a, st, hc.report(), route)) return rc;
+    TMF_HIP(hipMemcpyAsync(out_tiles, dout.p, obytes, hipMemcpyDeviceToHost, st));
+    return hc.finish();
 }
 
 extern "C++" {
@@ -1333,10 +1330,7 @@ int tmfwm_prepare_tiles(const uint8_t *wm, int64_t n_wm, int32_t wm_height, int3
         dstride = (int64_t)tbytes;
         if (int rc = dwm.alloc(wbytes * (size_t)n_wm, st, "watermarks")) return rc;
         if (int rc = dtile.alloc(tbytes * (size_t)n_wm, st, "tiles")) return rc;
-        if (n_wm == 1 || wm_stride == sstride)
-            TMF_HIP(hipMemcpyAsync(dwm.p, wm, wbytes * (size_t)n_wm, hipMemcpyHostToDevice, st));
-        else
-            TMF_HIP(hipMemcpy2DAsync(dwm.p, wbytes, wm, (size_t)wm_stride, wbytes, (size_t)n_wm, hipMemcpyHostToDevice, st));
+        if (int rc = copy_items(dwm.p, wm, wbytes, n_wm, wm_stride, hipMemcpyHostToDevice, st)) return rc;
         src = static_cast<const uint8_t *>(dwm.p);
         dst = static_cast<uint8_t *>(dtile.p);
     }
@@ -1351,10 +1345,7 @@ int tmfwm_prepare_tiles(const uint8_t *wm, int64_t n_wm, int32_t wm_height, int3
                                              static_cast<uint8_t *>(dtmp.p), dst + (size_t)py * tile_width + px, tile_width, dstride,
                                              st));
     if (mem_kind == TMFWM_MEM_HOST) {
-        if (n_wm == 1 || tile_stride == dstride)
-            TMF_HIP(hipMemcpyAsync(tiles, dst, tbytes * (size_t)n_wm, hipMemcpyDeviceToHost, st));
-        else
-            TMF_HIP(hipMemcpy2DAsync(tiles, (size_t)tile_stride, dst, tbytes, tbytes, (size_t)n_wm, hipMemcpyDeviceToHost, st));
+        if (int rc = copy_items(dst, tiles, tbytes, n_wm, tile_stride, hipMemcpyDeviceToHost, st)) return rc;
     }
     // the host-side tables (and, for the host path, the result) must outlive the copies
     TMF_HIP(hipStreamSynchronize(st));
@@ -1387,13 +1378,7 @@ struct RFrame {
 int check_ragged_call(const void *frames, int64_t n, int32_t block, double alpha, bool extract, int32_t mem_kind, int32_t route,
                       int64_t *n_lapack)
 {
-    if (route < TMFWM_ROUTE_HYBRID || route > TMFWM_ROUTE_RANK1_REFERENCE) return fail(TMFWM_ERR_INVALID, "route %d", route);
-    if (route == TMFWM_ROUTE_RANK1 || route == TMFWM_ROUTE_RANK1_REFERENCE)
-        return fail(TMFWM_ERR_UNSUPPORTED, "the ragged calls do not take the rank-1 routes yet (route %d)", route);
-    if (n_lapack) {
-        *n_lapack = 0;
-        t_list_pass = 0;  // no list pass in a ragged call
-    }
+    if (int rc = begin_call(route, n_lapack, false)) return rc;  // no rank-1 routes yet; no list pass in a ragged call
     if (n < 0) return fail(TMFWM_ERR_INVALID, "negative size (n=%lld)", (long long)n);
     if (n > 0 && !frames) return fail(TMFWM_ERR_INVALID, "frames is NULL");
     if (!supported_block(block)) return fail(TMFWM_ERR_UNSUPPORTED, "block size %d not supported (even, 4..16)", block);
@@ -1570,32 +1555,26 @@ void plan_ragged(const std::vector<RFrame> &fr, int32_t block, bool extract, std
     if (c.n > 0) chunks.push_back(c);
 }
 
-// Both passes of a ragged call over device-resident frames; counts as run_embed / run_extract
-// (read back when the caller asks for the count or `check` is set; `sink` takes them instead).
-int run_ragged(int32_t block, double alpha, bool extract, hipStream_t st, int route,
-               int64_t *n_lapack, bool check, uint32_t *sink, const std::vector<tmf::RaggedFrame> &table,
-               const std::vector<RaggedChunk> &chunks)
+// Both passes of a ragged call over device-resident frames: the frame table uploaded, then the
+// chunks through two_pass, with the edge pass between a chunk's first pass and its fixup pass and
+// neither of the two for a chunk without a block.
+int run_ragged(int32_t block, double alpha, bool extract, hipStream_t st, int route, const Report &rep,
+               const std::vector<tmf::RaggedFrame> &table, const std::vector<RaggedChunk> &chunks)
 {
-    const int64_t nch = (int64_t)chunks.size();
-    if (nch == 0) return 0;
-    int64_t max_blocks = 0;
-    for (const RaggedChunk &c : chunks) max_blocks = std::max(max_blocks, c.blocks);
+    if (chunks.empty()) return 0;
     const size_t tbytes = table.size() * sizeof(tmf::RaggedFrame);
     TableSlot slot;
     if (int rc = take_table(tbytes, stream_device(st), slot)) return rc;
     std::copy(table.begin(), table.end(), static_cast<tmf::RaggedFrame *>(slot.p));
-    DevBuf dtable, list, counts;
+    DevBuf dtable;
     int rc = dtable.alloc(tbytes, st, "frame table");
     if (rc == 0 && hipMemcpyAsync(dtable.p, slot.p, tbytes, hipMemcpyHostToDevice, st) != hipSuccess)
         rc = fail(TMFWM_ERR_HIP, "copying the frame table failed: %s", hipGetErrorString(hipGetLastError()));
     give_table(slot, st);
     if (rc) return rc;
-    if (max_blocks > 0) {
-        if (int r2 = list.alloc((size_t)max_blocks * 4, st, "dgesdd-route block list")) return r2;
-    }
-    if (int r2 = counts.alloc((size_t)nch * 12, st, "block-list counts")) return r2;  // as run_embed's
-    TMF_HIP(hipMemsetAsync(counts.p, 0, (size_t)nch * 12, st));
-    for (int64_t c = 0; c < nch; ++c) {
+    std::vector<int64_t> blocks;
+    for (const RaggedChunk &k : chunks) blocks.push_back(k.blocks);
+    return two_pass(blocks, false, true, st, rep, [&](int64_t c, const ChunkLists &w) -> int {
         const RaggedChunk &k = chunks[(size_t)c];
         tmf::RaggedArgs r{};
         r.frames = static_cast<const tmf::RaggedFrame *>(dtable.p) + k.first;
@@ -1603,26 +1582,19 @@ int run_ragged(int32_t block, double alpha, bool extract, hipStream_t st, int ro
         r.block = block;
         r.alpha = alpha;
         r.alpha32 = (float)alpha;
-        r.fb_list = static_cast<uint32_t *>(list.p);
-        r.fb_count = static_cast<uint32_t *>(counts.p) + c;
-        r.fb_bad = static_cast<uint32_t *>(counts.p) + nch + c;
+        r.fb_list = w.fb_list;  // no list pass in a ragged call
+        r.fb_count = w.fb_count;
+        r.fb_bad = w.fb_bad;
         if (k.blocks > 0) {
             if (route == TMFWM_ROUTE_REFERENCE) TMF_HIP(tmf::launch_list_all(r.fb_list, r.fb_count, k.blocks, st));
             else TMF_HIP(extract ? tmf::launch_extract_ragged(r, k.waves, st) : tmf::launch_embed_ragged(r, k.waves, st));
         }
         if (!extract) TMF_HIP(tmf::launch_edges_ragged(r, k.edge, st));
-        if (k.blocks > 0) {
+        if (k.blocks > 0)
             TMF_HIP(extract ? tmf::launch_extract_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st)
                             : tmf::launch_embed_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st));
-            if (force_nonconv()) TMF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(r.fb_bad), 1, 1, st));
-        }
-    }
-    if (sink) {
-        TMF_HIP(hipMemcpyAsync(sink, counts.p, (size_t)nch * 12, hipMemcpyDeviceToHost, st));
         return 0;
-    }
-    if (n_lapack || check) return sum_counts(static_cast<const uint32_t *>(counts.p), nch, st, n_lapack);
-    return 0;
+    });
 }
 
 size_t round16(size_t n) { return (n + 15) & ~size_t(15); }
@@ -1640,7 +1612,7 @@ int ragged_call(std::vector<RFrame> &fr, int32_t block, double alpha, bool extra
     if (mem_kind == TMFWM_MEM_DEVICE) {
         if (int rc = check_ragged_device(fr, block, extract)) return rc;
         plan_ragged(fr, block, extract, table, chunks);
-        return run_ragged(block, alpha, extract, st, route, n_lapack, false, nullptr, table, chunks);
+        return run_ragged(block, alpha, extract, st, route, device_report(n_lapack), table, chunks);
     }
     // host memory: every buffer of the call in one device allocation (16-byte aligned pieces),
     // results copied back, one synchronisation
@@ -1668,17 +1640,15 @@ int ragged_call(std::vector<RFrame> &fr, int32_t block, double alpha, bool extra
         if (extract || tb) TMF_HIP(hipMemcpyAsync(base + off[3 * i + 1], fr[i].in1, extract ? px : tb, hipMemcpyHostToDevice, st));
     }
     plan_ragged(dv, block, extract, table, chunks);
-    const int64_t nch = (int64_t)chunks.size();
-    HostSink sink(nch, st);
-    if (int rc = run_ragged(block, alpha, extract, st, route, n_lapack, true, sink.p, table, chunks)) return rc;
+    HostCall hc((int64_t)chunks.size(), st, n_lapack);
+    if (int rc = run_ragged(block, alpha, extract, st, route, hc.report(), table, chunks)) return rc;
     for (size_t i = 0; i < fr.size(); ++i) {
         const size_t px = (size_t)fr[i].pixel_bytes(), tb = (size_t)fr[i].tile_bytes(block);
         const size_t ob = extract ? tb : px;
         if (px == 0 || ob == 0) continue;
         TMF_HIP(hipMemcpyAsync(fr[i].out, dv[i].out, ob, hipMemcpyDeviceToHost, st));
     }
-    TMF_HIP(hipStreamSynchronize(st));
-    return sink.p && nch ? tmf::sum_sink(sink.p, nch, n_lapack) : 0;
+    return hc.finish();
 }
 
 }  // namespace
@@ -1687,7 +1657,6 @@ int ragged_call(std::vector<RFrame> &fr, int32_t block, double alpha, bool extra
 int tmfwm_embed_ragged(const tmfwm_embed_frame *frames, int64_t n_frames, int32_t block, double alpha, int32_t mem_kind,
                        void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
 {
-    t_err.clear();
     if (int rc = check_ragged_call(frames, n_frames, block, alpha, false, mem_kind, route, n_lapack_blocks)) return rc;
     std::vector<RFrame> fr((size_t)n_frames);  // the library's copy: the caller's array is not read again
     for (int64_t i = 0; i < n_frames; ++i) fr[(size_t)i] = {frames[i].rgb, frames[i].wm_tile, frames[i].out, frames[i].height, frames[i].width};
@@ -1697,7 +1666,6 @@ int tmfwm_embed_ragged(const tmfwm_embed_frame *frames, int64_t n_frames, int32_
 int tmfwm_extract_ragged(const tmfwm_extract_frame *frames, int64_t n_frames, int32_t block, double alpha, int32_t mem_kind,
                          void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
 {
-    t_err.clear();
     if (int rc = check_ragged_call(frames, n_frames, block, alpha, true, mem_kind, route, n_lapack_blocks)) return rc;
     std::vector<RFrame> fr((size_t)n_frames);
     for (int64_t i = 0; i < n_frames; ++i)
