@@ -255,7 +255,8 @@ constexpr int kEmbedTS1 = ((kParkD<B> && kParkOff<Geo<B>::L> + B * B > kEmbedTS0
 // Bank spreading for the reconstruction's LDS reads (ds_read_b32: bank = dword address mod 32
 // over each 32-lane half): at b = 8 a half holds 16 blocks, at b = 16 four, and each lane reads
 // its block's lower-end or upper-end tile.  Tile strides 73 (b = 8: 9 g mod 32, distinct over
-// 16 blocks) and 344 (b = 16: 24 g mod 32; the scratch it must hold rounded up to that) in both regions, with the upper-end region kHiPad dwords
+// 16 blocks) and 312 (b = 16: 24 g mod 32; the scratch it must hold rounded up to that, which it
+// already is) in both regions, with the upper-end region kHiPad dwords
 // further on (16 / 4), put every (block, end) of a half on a bank of its own; with strides 72
 // and 72 (b = 16: 312 and 272) four (two) of them shared one, and bank conflicts were 75 % of
 // embed<8>'s LDS cycles (profiles/r05/r05h).

@@ -1,48 +1,21 @@
 // The dgesdd route on the GPU: dispatch of the second passes (tmfwm_fixup.h, one TU per block
-// size: tmfwm_fixup<b>.hip) and the stage entry points the parity tests call.
-#include "tmfwm_fixup.h"
+// size, tmfwm_fixup.hip: this unit does not see their kernels) and the stage entry points the
+// parity tests call.
+#include "tmfwm_internal.h"
+#include "tmfwm_lapack.h"
 
 #include <cstdlib>
 
 namespace tmf {
 
-#define TMF_FIXUP_DECL(B)                                                                                                    \
-    hipError_t launch_embed_fixup_##B(const EmbedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);          \
-    hipError_t launch_extract_fixup_##B(const ExtractArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
-TMF_FIXUP_DECL(4)
-TMF_FIXUP_DECL(6)
-TMF_FIXUP_DECL(8)
-TMF_FIXUP_DECL(10)
-TMF_FIXUP_DECL(12)
-TMF_FIXUP_DECL(14)
-TMF_FIXUP_DECL(16)
-
 hipError_t launch_embed_fixup(const EmbedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st)
 {
-    switch (a.block) {
-    case 4: return launch_embed_fixup_4(a, list, count, max_entries, st);
-    case 6: return launch_embed_fixup_6(a, list, count, max_entries, st);
-    case 8: return launch_embed_fixup_8(a, list, count, max_entries, st);
-    case 10: return launch_embed_fixup_10(a, list, count, max_entries, st);
-    case 12: return launch_embed_fixup_12(a, list, count, max_entries, st);
-    case 14: return launch_embed_fixup_14(a, list, count, max_entries, st);
-    case 16: return launch_embed_fixup_16(a, list, count, max_entries, st);
-    default: return hipErrorInvalidValue;
-    }
+    return for_block(a.block, [&](auto b) { return embed_fixup_b<b()>(a, list, count, max_entries, st); });
 }
 
 hipError_t launch_extract_fixup(const ExtractArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st)
 {
-    switch (a.block) {
-    case 4: return launch_extract_fixup_4(a, list, count, max_entries, st);
-    case 6: return launch_extract_fixup_6(a, list, count, max_entries, st);
-    case 8: return launch_extract_fixup_8(a, list, count, max_entries, st);
-    case 10: return launch_extract_fixup_10(a, list, count, max_entries, st);
-    case 12: return launch_extract_fixup_12(a, list, count, max_entries, st);
-    case 14: return launch_extract_fixup_14(a, list, count, max_entries, st);
-    case 16: return launch_extract_fixup_16(a, list, count, max_entries, st);
-    default: return hipErrorInvalidValue;
-    }
+    return for_block(a.block, [&](auto b) { return extract_fixup_b<b()>(a, list, count, max_entries, st); });
 }
 
 // The reference route (TMFWM_ROUTE_REFERENCE): every block of the launch on the dgesdd route.

@@ -1,6 +1,7 @@
 // The dgesdd route on the GPU (tmfwm_lapack.h): the second-pass kernels of embed and
-// extract and their launch templates.  Instantiated per block size in tmfwm_fixup<b>.hip
-// (compiled in parallel); tmfwm_fallback.hip dispatches and holds the stage entry points.
+// extract: their per-block device functions and the walk over the list.  The kernels are compiled
+// per block size (tmfwm_fixup.hip with -DTMF_B=<b>, in parallel); tmfwm_fallback.hip dispatches
+// and holds the stage entry points.
 //
 // embed_kernel<b> runs the Jacobi route on every block and appends to a list the blocks
 // whose conditioning test fails; embed_fixup_kernel<b> redoes exactly
@@ -213,49 +214,38 @@ TMF_DEVI void extract_fix_block(const ExtractArgs &a, uint32_t id, FixLdsS<B> &f
     }
 }
 
-// A short list (the hybrid route's few flagged blocks: no more than the grid's workgroups) takes
-// a whole wave per block -- the lowest latency per block, and the pass is one block's latency;
-// a long one (the reference route: every block) takes 64 / G blocks per wave for throughput.
-// The choice is uniform over the grid (the device-side count against the grid size).
-template <int B>
-__global__ __launch_bounds__(64) void embed_fixup_kernel(EmbedArgs a, const uint32_t *__restrict__ list, const uint32_t *__restrict__ count)
-{
-    constexpr int G = kFixLanes<B>, NG = 64 / G;
-    static_assert(G >= B, "a group holds one element of dbdsqr's vectors per lane");
-    __shared__ FixLds<B> fl[NG];
-    const uint32_t n = *count;
-    if (n <= gridDim.x) {
-        if (blockIdx.x < n) embed_fix_block<B, lp::WavePar, 64>(a, list[blockIdx.x], fl[0], (int)threadIdx.x);
-        return;
-    }
-    const int gl = lp::GroupPar<G>::lane(), grp = (int)(threadIdx.x / G);
-    for (uint32_t t0 = blockIdx.x * NG; t0 < n; t0 += gridDim.x * NG) {
-        const uint32_t t = t0 + (uint32_t)grp;
-        if (t < n) embed_fix_block<B, lp::GroupPar<G>, G>(a, list[t], fl[grp], gl);  // else: no block this round
-    }
-}
+// The walk of every dgesdd-route pass over its list.  A short list (the hybrid route's few
+// flagged blocks: no more than the grid's workgroups) takes a whole wave per block -- the lowest
+// latency per block, and the pass is one block's latency; a long one (the reference route: every
+// block) takes 64 / G blocks per wave for throughput.  The choice is uniform over the grid (the
+// device-side count against the grid size).  body(par, id, lds, gl) does listed block `id` on
+// lanes gl = 0 .. par.G - 1 under lane policy decltype(par)::Par, with `lds` (an Lds) to itself.
+template <class P, int N>
+struct FixPar {
+    using Par = P;
+    static constexpr int G = N;
+};
 
-template <int B>
-__global__ __launch_bounds__(64) void extract_fixup_kernel(ExtractArgs a, const uint32_t *__restrict__ list,
-                                                           const uint32_t *__restrict__ count)
+template <int B, class Lds, class Body>
+TMF_DEVI void fixup_walk(const uint32_t *__restrict__ list, const uint32_t *__restrict__ count, Body body)
 {
     constexpr int G = kFixLanes<B>, NG = 64 / G;
     static_assert(G >= B, "a group holds one element of dbdsqr's vectors per lane");
-    __shared__ FixLdsS<B> fl[NG];
+    __shared__ Lds fl[NG];
     const uint32_t n = *count;
     if (n <= gridDim.x) {
-        if (blockIdx.x < n) extract_fix_block<B, lp::WavePar, 64>(a, list[blockIdx.x], fl[0], (int)threadIdx.x);
+        if (blockIdx.x < n) body(FixPar<lp::WavePar, 64>{}, list[blockIdx.x], fl[0], (int)threadIdx.x);
         return;
     }
     const int gl = lp::GroupPar<G>::lane(), grp = (int)(threadIdx.x / G);
     for (uint32_t t0 = blockIdx.x * NG; t0 < n; t0 += gridDim.x * NG) {
         const uint32_t t = t0 + (uint32_t)grp;
-        if (t < n) extract_fix_block<B, lp::GroupPar<G>, G>(a, list[t], fl[grp], gl);
+        if (t < n) body(FixPar<lp::GroupPar<G>, G>{}, list[t], fl[grp], gl);  // else: no block this round
     }
 }
 
 // ---------------------------------------------------------------------------
-// launchers: the grid is sized for the listed blocks the chip holds at once (capped by the
+// the launchers' grid is sized for the listed blocks the chip holds at once (capped by the
 // possible list length); workgroups past the device-side count exit at once, the others
 // stride over it
 // ---------------------------------------------------------------------------
@@ -266,17 +256,11 @@ inline unsigned fixup_grid(int64_t entries)
     return (unsigned)(waves < 1 ? 1 : (waves > 8192 ? 8192 : waves));
 }
 
-template <int B>
-inline hipError_t embed_fixup_b(const EmbedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st)
+template <int B, class Args>
+inline hipError_t launch_fixup(void (*kernel)(Args, const uint32_t *, const uint32_t *), const Args &a, const uint32_t *list,
+                               const uint32_t *count, int64_t max_entries, hipStream_t st)
 {
-    hipLaunchKernelGGL((embed_fixup_kernel<B>), dim3(fixup_grid<B>(max_entries)), dim3(64), 0, st, a, list, count);
-    return hipGetLastError();
-}
-
-template <int B>
-inline hipError_t extract_fixup_b(const ExtractArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st)
-{
-    hipLaunchKernelGGL((extract_fixup_kernel<B>), dim3(fixup_grid<B>(max_entries)), dim3(64), 0, st, a, list, count);
+    hipLaunchKernelGGL(kernel, dim3(fixup_grid<B>(max_entries)), dim3(64), 0, st, a, list, count);
     return hipGetLastError();
 }
 

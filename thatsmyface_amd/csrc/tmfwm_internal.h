@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/tmfwm.h"
+#include "tmfwm_sizes.h"
 
 namespace tmf {
 
@@ -117,6 +118,37 @@ int extract_device_async(const uint8_t *wsrc, const uint8_t *osrc, int64_t n, in
                          double alpha, uint8_t *out, hipStream_t st, uint32_t *sink, int route = TMFWM_ROUTE_HYBRID);
 int sum_sink(const uint32_t *sink, int64_t nchunks, int64_t *lapack);  // TMFWM_ERR_HIP on non-convergence
 
+// ---- launch shapes shared by the launchers (host side)
+
+// A grid's y dimension takes at most 65535 frames.  The C ABI's chunks never hold more
+// (tmfwm_capi.cpp, Chunks::plan), and the strip launchers refuse more: a listed block's id is
+// relative to its launch, so a chunk cut into several strip launches would hand its list pass ids
+// of the wrong frames.  Launches that keep no list (edge pixels, synthetic frames) are cut here.
+constexpr int64_t kMaxGridY = 65535;
+
+// launch(f0, nf) for frames [f0, f0 + nf) in slices of at most kMaxGridY frames
+template <class Launch>
+inline hipError_t for_frame_slices(int64_t nframes, Launch launch)
+{
+    for (int64_t f0 = 0; f0 < nframes; f0 += kMaxGridY) launch(f0, nframes - f0 < kMaxGridY ? nframes - f0 : kMaxGridY);
+    return hipGetLastError();
+}
+
+// the list pass's grid: one wave per segment that can hold a block row (the others stay empty)
+inline unsigned list_grid(int64_t rows) { return (unsigned)(rows < (int64_t)kListShards ? rows : (int64_t)kListShards); }
+
+// The strip pass of a chunk -- one wave per strip of bpw blocks, frames on the grid's y -- and
+// then, if the chunk has one (`list` and a.slow_list set), the list pass over what it deferred.
+template <class Args>
+inline hipError_t launch_strips(Args a, int bpw, void (*strip)(Args), void (*list)(Args), hipStream_t st)
+{
+    if (a.nframes > kMaxGridY) return hipErrorInvalidValue;
+    a.strips_per_row = (a.nbw + bpw - 1) / bpw;
+    hipLaunchKernelGGL(strip, dim3((unsigned)((int64_t)a.strips_per_row * a.nbh), (unsigned)a.nframes), dim3(64), 0, st, a);
+    if (list && a.slow_list) hipLaunchKernelGGL(list, dim3(list_grid(a.nframes * a.nbh)), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_embed(const EmbedArgs &a, hipStream_t st);
 hipError_t launch_embed_rank1(EmbedArgs a, hipStream_t st);  // TMFWM_ROUTE_RANK1 (tmfwm_rank1.hip)
 bool rank1_block(int block);  // the block sizes TMFWM_ROUTE_RANK1 has a pre-pass for
@@ -130,6 +162,16 @@ hipError_t launch_dct2d_blocks(float *blocks, int64_t nb, int block, int inverse
 // second pass on the dgesdd route (tmfwm_fallback.hip); max_entries bounds the list
 hipError_t launch_embed_fixup(const EmbedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
 hipError_t launch_extract_fixup(const ExtractArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
+// their launchers per block size B: declared here, defined and instantiated for B = TMF_B in the
+// size's own translation unit (tmfwm_fixup.hip, tmfwm_keyed_fixup.hip), which alone sees the kernels
+template <int B>
+hipError_t embed_fixup_b(const EmbedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
+template <int B>
+hipError_t extract_fixup_b(const ExtractArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
+template <int B>
+hipError_t sigma1_fixup_b(const KeyedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
+template <int B>
+hipError_t extract_keyed_fixup_b(const KeyedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
 // keyed extraction (tmfwm_keyed.hip; the dgesdd-route passes per block size: tmfwm_keyed_fixup.hip)
 hipError_t launch_sigma1_map(const KeyedArgs &a, hipStream_t st);
 hipError_t launch_extract_keyed(const KeyedArgs &a, hipStream_t st);

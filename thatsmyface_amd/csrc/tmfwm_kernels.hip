@@ -241,55 +241,21 @@ __global__ __launch_bounds__(256) void synth_kernel(uint64_t seed, int64_t frame
 // ---------------------------------------------------------------------------
 // Launchers (host side of this TU)
 // ---------------------------------------------------------------------------
-template <int B>
-static hipError_t launch_embed_b(EmbedArgs a, hipStream_t st)
-{
-    a.strips_per_row = (a.nbw + Geo<B>::BPW - 1) / Geo<B>::BPW;
-    const int64_t gx = (int64_t)a.strips_per_row * a.nbh;
-    for (int64_t f0 = 0; f0 < a.nframes; f0 += 65535) {
-        EmbedArgs c = a;
-        const int64_t nf = a.nframes - f0 < 65535 ? a.nframes - f0 : 65535;
-        c.src = a.src + f0 * a.frame_stride;
-        c.dst = a.dst + f0 * a.frame_stride;
-        c.wm = a.wm + f0 * a.wm_stride;
-        hipLaunchKernelGGL((embed_kernel<B, false>), dim3((unsigned)gx, (unsigned)nf), dim3(64), 0, st, c);
-    }
-    if (kDeferMax<B> > 0 && a.slow_list) {  // the list pass over the blocks the first pass left unfinished (ids relative to a.src)
-        const int64_t rows = a.nframes * a.nbh;  // one wave per segment (2 per SIMD fill the chip)
-        const unsigned grid = (unsigned)(rows < (int64_t)kListShards ? rows : (int64_t)kListShards);
-        if constexpr (kDeferMax<B> > 0) hipLaunchKernelGGL((embed_kernel<B, true>), dim3(grid), dim3(64), 0, st, a);
-    }
-    return hipGetLastError();
-}
-
 bool embed_defers(int block)
 {
-    switch (block) {
-    case 4: return kDeferMax<4> > 0;
-    case 6: return kDeferMax<6> > 0;
-    case 8: return kDeferMax<8> > 0;
-    case 10: return kDeferMax<10> > 0;
-    case 12: return kDeferMax<12> > 0;
-    case 14: return kDeferMax<14> > 0;
-    case 16: return kDeferMax<16> > 0;
-    default: return false;
-    }
+    return block_value(block, false, [](auto b) { return kDeferMax<b()> > 0; });
 }
 
 hipError_t launch_embed(const EmbedArgs &a, hipStream_t st)
 {
-    hipError_t e = hipSuccess;
     if (a.nbh > 0 && a.nbw > 0) {
-        switch (a.block) {
-        case 4: e = launch_embed_b<4>(a, st); break;
-        case 6: e = launch_embed_b<6>(a, st); break;
-        case 8: e = launch_embed_b<8>(a, st); break;
-        case 10: e = launch_embed_b<10>(a, st); break;
-        case 12: e = launch_embed_b<12>(a, st); break;
-        case 14: e = launch_embed_b<14>(a, st); break;
-        case 16: e = launch_embed_b<16>(a, st); break;
-        default: return hipErrorInvalidValue;
-        }
+        // the list pass takes the blocks the first pass left unfinished (ids relative to a.src)
+        const hipError_t e = for_block(a.block, [&](auto b) {
+            constexpr int B = b();
+            void (*list)(EmbedArgs) = nullptr;
+            if constexpr (kDeferMax<B> > 0) list = embed_kernel<B, true>;
+            return launch_strips(a, Geo<B>::BPW, embed_kernel<B, false>, list, st);
+        });
         if (e != hipSuccess) return e;
     }
     return launch_edges(a.src, a.dst, a.nframes, a.H, a.W, a.frame_stride, a.block, st);
@@ -308,50 +274,21 @@ hipError_t launch_edges(const uint8_t *src, uint8_t *dst, int64_t nframes, int H
     e.edge_w = W - e.core_w;
     const int64_t n = (int64_t)e.core_h * e.edge_w + (int64_t)(H - e.core_h) * W;
     if (n == 0) return hipSuccess;
-    for (int64_t f0 = 0; f0 < nframes; f0 += 65535) {
+    return for_frame_slices(nframes, [&](int64_t f0, int64_t nf) {
         EdgeArgs c = e;
         c.src = src + f0 * frame_stride;
         c.dst = dst + f0 * frame_stride;
-        const int64_t nf = nframes - f0 < 65535 ? nframes - f0 : 65535;
         hipLaunchKernelGGL(edge_roundtrip_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)nf), dim3(256), 0, st, c);
-    }
-    return hipGetLastError();
-}
-
-template <int B>
-static hipError_t launch_extract_b(ExtractArgs a, hipStream_t st)
-{
-    a.strips_per_row = (a.nbw + Geo<B>::BPW - 1) / Geo<B>::BPW;
-    const int64_t gx = (int64_t)a.strips_per_row * a.nbh;
-    for (int64_t f0 = 0; f0 < a.nframes; f0 += 65535) {
-        ExtractArgs c = a;
-        const int64_t nf = a.nframes - f0 < 65535 ? a.nframes - f0 : 65535;
-        c.wsrc = a.wsrc + f0 * a.frame_stride;
-        c.osrc = a.osrc + f0 * a.frame_stride;
-        c.out = a.out + f0 * a.tile_stride;
-        hipLaunchKernelGGL((extract_kernel<B, false>), dim3((unsigned)gx, (unsigned)nf), dim3(64), 0, st, c);
-    }
-    if (a.slow_list) {  // the list pass over the undecided blocks (ids relative to a.wsrc / a.osrc)
-        const int64_t rows = a.nframes * a.nbh;  // segments past the rows stay empty
-        const unsigned grid = (unsigned)(rows < (int64_t)kListShards ? rows : (int64_t)kListShards);
-        hipLaunchKernelGGL((extract_kernel<B, true>), dim3(grid), dim3(64), 0, st, a);
-    }
-    return hipGetLastError();
+    });
 }
 
 hipError_t launch_extract(const ExtractArgs &a, hipStream_t st)
 {
     if (a.nbh == 0 || a.nbw == 0) return hipSuccess;
-    switch (a.block) {
-    case 4: return launch_extract_b<4>(a, st);
-    case 6: return launch_extract_b<6>(a, st);
-    case 8: return launch_extract_b<8>(a, st);
-    case 10: return launch_extract_b<10>(a, st);
-    case 12: return launch_extract_b<12>(a, st);
-    case 14: return launch_extract_b<14>(a, st);
-    case 16: return launch_extract_b<16>(a, st);
-    default: return hipErrorInvalidValue;
-    }
+    // the list pass takes the undecided blocks (ids relative to a.wsrc / a.osrc)
+    return for_block(a.block, [&](auto b) {
+        return launch_strips(a, Geo<b()>::BPW, extract_kernel<b(), false>, extract_kernel<b(), true>, st);
+    });
 }
 
 hipError_t launch_rgb_to_ycbcr(const uint8_t *rgb, int64_t npix, float *ycc, hipStream_t st)
@@ -387,51 +324,27 @@ hipError_t launch_ycbcr_to_rgb(const void *ycc, int dtype, int64_t npix, uint8_t
     return hipGetLastError();
 }
 
-template <int B>
-static hipError_t launch_dct_b(float *blocks, int64_t nb, int inverse, hipStream_t st)
-{
-    const unsigned grid = (unsigned)((nb + Geo<B>::BPW - 1) / Geo<B>::BPW);
-    if (inverse) hipLaunchKernelGGL((dct2d_blocks_kernel<B, true>), dim3(grid), dim3(64), 0, st, blocks, nb);
-    else hipLaunchKernelGGL((dct2d_blocks_kernel<B, false>), dim3(grid), dim3(64), 0, st, blocks, nb);
-    return hipGetLastError();
-}
-
 hipError_t launch_dct2d_blocks(float *blocks, int64_t nb, int block, int inverse, hipStream_t st)
 {
     if (nb == 0) return hipSuccess;
-    switch (block) {
-    case 4: return launch_dct_b<4>(blocks, nb, inverse, st);
-    case 6: return launch_dct_b<6>(blocks, nb, inverse, st);
-    case 8: return launch_dct_b<8>(blocks, nb, inverse, st);
-    case 10: return launch_dct_b<10>(blocks, nb, inverse, st);
-    case 12: return launch_dct_b<12>(blocks, nb, inverse, st);
-    case 14: return launch_dct_b<14>(blocks, nb, inverse, st);
-    case 16: return launch_dct_b<16>(blocks, nb, inverse, st);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-template <int B>
-static hipError_t launch_svd_b(const float *D, int64_t nb, float *U, float *S, float *Vt, int32_t *sweeps, hipStream_t st)
-{
-    const unsigned grid = (unsigned)((nb + Geo<B>::BPW - 1) / Geo<B>::BPW);
-    hipLaunchKernelGGL(svd_blocks_kernel<B>, dim3(grid), dim3(64), 0, st, D, nb, U, S, Vt, sweeps);
-    return hipGetLastError();
+    return for_block(block, [&](auto b) {
+        constexpr int B = b();
+        const unsigned grid = (unsigned)((nb + Geo<B>::BPW - 1) / Geo<B>::BPW);
+        if (inverse) hipLaunchKernelGGL((dct2d_blocks_kernel<B, true>), dim3(grid), dim3(64), 0, st, blocks, nb);
+        else hipLaunchKernelGGL((dct2d_blocks_kernel<B, false>), dim3(grid), dim3(64), 0, st, blocks, nb);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_svd_blocks(const float *D, int64_t nb, int block, float *U, float *S, float *Vt, int32_t *sweeps, hipStream_t st)
 {
     if (nb == 0) return hipSuccess;
-    switch (block) {
-    case 4: return launch_svd_b<4>(D, nb, U, S, Vt, sweeps, st);
-    case 6: return launch_svd_b<6>(D, nb, U, S, Vt, sweeps, st);
-    case 8: return launch_svd_b<8>(D, nb, U, S, Vt, sweeps, st);
-    case 10: return launch_svd_b<10>(D, nb, U, S, Vt, sweeps, st);
-    case 12: return launch_svd_b<12>(D, nb, U, S, Vt, sweeps, st);
-    case 14: return launch_svd_b<14>(D, nb, U, S, Vt, sweeps, st);
-    case 16: return launch_svd_b<16>(D, nb, U, S, Vt, sweeps, st);
-    default: return hipErrorInvalidValue;
-    }
+    return for_block(block, [&](auto b) {
+        constexpr int B = b();
+        const unsigned grid = (unsigned)((nb + Geo<B>::BPW - 1) / Geo<B>::BPW);
+        hipLaunchKernelGGL(svd_blocks_kernel<B>, dim3(grid), dim3(64), 0, st, D, nb, U, S, Vt, sweeps);
+        return hipGetLastError();
+    });
 }
 
 #ifdef TMF_STAMPS
@@ -451,11 +364,9 @@ hipError_t launch_synth(uint64_t seed, int64_t frame0, int64_t nframes, int64_t 
     if (nframes == 0 || frame_bytes == 0) return hipSuccess;
     const int64_t per = (frame_bytes + 1023) / 1024;
     const unsigned gx = (unsigned)(per < 4096 ? per : 4096);
-    for (int64_t f0 = 0; f0 < nframes; f0 += 65535) {
-        const int64_t nf = nframes - f0 < 65535 ? nframes - f0 : 65535;
+    return for_frame_slices(nframes, [&](int64_t f0, int64_t nf) {
         hipLaunchKernelGGL(synth_kernel, dim3(gx, (unsigned)nf), dim3(256), 0, st, seed, frame0 + f0, frame_bytes, out + f0 * frame_bytes);
-    }
-    return hipGetLastError();
+    });
 }
 
 }  // namespace tmf

@@ -94,93 +94,31 @@ __global__ __launch_bounds__(64, kKeyedWaves<B>) void extract_keyed_kernel(Keyed
     keyed_pass<B, LIST, false>(a);
 }
 
-// the strip pass in launches of at most 65535 frames (the grid's y limit; the frame pointers
-// move with each launch), then the list pass over the whole chunk (ids relative to a.src)
-template <int B, bool MAP>
-static hipError_t launch_keyed_b(KeyedArgs a, hipStream_t st)
-{
-    a.strips_per_row = (a.nbw + Geo<B>::BPW - 1) / Geo<B>::BPW;
-    const int64_t gx = (int64_t)a.strips_per_row * a.nbh;
-    for (int64_t f0 = 0; f0 < a.nframes; f0 += 65535) {
-        KeyedArgs c = a;
-        const int64_t nf = a.nframes - f0 < 65535 ? a.nframes - f0 : 65535;
-        c.src = a.src + f0 * a.frame_stride;
-        if constexpr (MAP) {
-            c.key_out = a.key_out + f0 * a.key_stride;
-            hipLaunchKernelGGL((sigma1_map_kernel<B, false>), dim3((unsigned)gx, (unsigned)nf), dim3(64), 0, st, c);
-        } else {
-            c.key = a.key + f0 * a.key_stride;
-            c.out = a.out + f0 * a.tile_stride;
-            hipLaunchKernelGGL((extract_keyed_kernel<B, false>), dim3((unsigned)gx, (unsigned)nf), dim3(64), 0, st, c);
-        }
-    }
-    if (a.slow_list) {
-        const int64_t rows = a.nframes * a.nbh;  // segments past the rows stay empty
-        const unsigned grid = (unsigned)(rows < (int64_t)kListShards ? rows : (int64_t)kListShards);
-        if constexpr (MAP) hipLaunchKernelGGL((sigma1_map_kernel<B, true>), dim3(grid), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((extract_keyed_kernel<B, true>), dim3(grid), dim3(64), 0, st, a);
-    }
-    return hipGetLastError();
-}
-
+// the strip pass, then the list pass over the whole chunk (ids relative to a.src)
 template <bool MAP>
 static hipError_t launch_keyed(const KeyedArgs &a, hipStream_t st)
 {
     if (a.nbh == 0 || a.nbw == 0) return hipSuccess;
-    switch (a.block) {
-    case 4: return launch_keyed_b<4, MAP>(a, st);
-    case 6: return launch_keyed_b<6, MAP>(a, st);
-    case 8: return launch_keyed_b<8, MAP>(a, st);
-    case 10: return launch_keyed_b<10, MAP>(a, st);
-    case 12: return launch_keyed_b<12, MAP>(a, st);
-    case 14: return launch_keyed_b<14, MAP>(a, st);
-    case 16: return launch_keyed_b<16, MAP>(a, st);
-    default: return hipErrorInvalidValue;
-    }
+    return for_block(a.block, [&](auto b) {
+        constexpr int B = b();
+        if constexpr (MAP) return launch_strips(a, Geo<B>::BPW, sigma1_map_kernel<B, false>, sigma1_map_kernel<B, true>, st);
+        else return launch_strips(a, Geo<B>::BPW, extract_keyed_kernel<B, false>, extract_keyed_kernel<B, true>, st);
+    });
 }
 
 hipError_t launch_sigma1_map(const KeyedArgs &a, hipStream_t st) { return launch_keyed<true>(a, st); }
 hipError_t launch_extract_keyed(const KeyedArgs &a, hipStream_t st) { return launch_keyed<false>(a, st); }
 
 // the dgesdd-route passes, one TU per block size (tmfwm_keyed_fixup.hip)
-#define TMF_KEYED_FIXUP_DECL(B)                                                                                      \
-    hipError_t launch_sigma1_fixup_##B(const KeyedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t); \
-    hipError_t launch_extract_keyed_fixup_##B(const KeyedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
-TMF_KEYED_FIXUP_DECL(4)
-TMF_KEYED_FIXUP_DECL(6)
-TMF_KEYED_FIXUP_DECL(8)
-TMF_KEYED_FIXUP_DECL(10)
-TMF_KEYED_FIXUP_DECL(12)
-TMF_KEYED_FIXUP_DECL(14)
-TMF_KEYED_FIXUP_DECL(16)
-
 hipError_t launch_sigma1_fixup(const KeyedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st)
 {
-    switch (a.block) {
-    case 4: return launch_sigma1_fixup_4(a, list, count, max_entries, st);
-    case 6: return launch_sigma1_fixup_6(a, list, count, max_entries, st);
-    case 8: return launch_sigma1_fixup_8(a, list, count, max_entries, st);
-    case 10: return launch_sigma1_fixup_10(a, list, count, max_entries, st);
-    case 12: return launch_sigma1_fixup_12(a, list, count, max_entries, st);
-    case 14: return launch_sigma1_fixup_14(a, list, count, max_entries, st);
-    case 16: return launch_sigma1_fixup_16(a, list, count, max_entries, st);
-    default: return hipErrorInvalidValue;
-    }
+    return for_block(a.block, [&](auto b) { return sigma1_fixup_b<b()>(a, list, count, max_entries, st); });
 }
 
 hipError_t launch_extract_keyed_fixup(const KeyedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries,
                                       hipStream_t st)
 {
-    switch (a.block) {
-    case 4: return launch_extract_keyed_fixup_4(a, list, count, max_entries, st);
-    case 6: return launch_extract_keyed_fixup_6(a, list, count, max_entries, st);
-    case 8: return launch_extract_keyed_fixup_8(a, list, count, max_entries, st);
-    case 10: return launch_extract_keyed_fixup_10(a, list, count, max_entries, st);
-    case 12: return launch_extract_keyed_fixup_12(a, list, count, max_entries, st);
-    case 14: return launch_extract_keyed_fixup_14(a, list, count, max_entries, st);
-    case 16: return launch_extract_keyed_fixup_16(a, list, count, max_entries, st);
-    default: return hipErrorInvalidValue;
-    }
+    return for_block(a.block, [&](auto b) { return extract_keyed_fixup_b<b()>(a, list, count, max_entries, st); });
 }
 
 }  // namespace tmf

@@ -1,14 +1,13 @@
-// dgesdd-route passes of keyed extraction (tmfwm_keyed.h) for one block size, TMF_KEYED_B:
-// compiled once per size (tmfwm_keyed_fixup<b>.o), as tmfwm_ragged_fixup.hip is.  Each listed
+// dgesdd-route passes of keyed extraction (tmfwm_keyed.h) for one block size, TMF_B:
+// compiled once per size (tmfwm_keyed_fixup<b>.o), as tmfwm_fixup.hip is.  Each listed
 // block's S[0] on the dgesdd route (np.linalg.svd's arithmetic), stored as its key entry
 // (sigma1_fixup_kernel) or turned into its byte against the stored entry
-// (extract_keyed_fixup_kernel).  The grid policy is extract_fixup_kernel's: a wave per block for
-// a short list, groups of kFixLanes<B> lanes for a long one.
+// (extract_keyed_fixup_kernel), on extract_fixup_kernel's walk over the list (fixup_walk).
 #include "tmfwm_fixup.h"
 #include "tmfwm_keyed.h"
 
-#ifndef TMF_KEYED_B
-#error "TMF_KEYED_B: the block size of this translation unit"
+#ifndef TMF_B
+#error "TMF_B: the block size of this translation unit"
 #endif
 
 namespace tmf {
@@ -31,19 +30,9 @@ TMF_DEVI void keyed_fix_block(const KeyedArgs &a, uint32_t id, FixLdsS<B> &f, in
 template <int B, bool MAP>
 TMF_DEVI void keyed_fixup(const KeyedArgs &a, const uint32_t *__restrict__ list, const uint32_t *__restrict__ count)
 {
-    constexpr int G = kFixLanes<B>, NG = 64 / G;
-    static_assert(G >= B, "a group holds one element of dbdsqr's vectors per lane");
-    __shared__ FixLdsS<B> fl[NG];
-    const uint32_t n = *count;
-    if (n <= gridDim.x) {
-        if (blockIdx.x < n) keyed_fix_block<B, lp::WavePar, 64, MAP>(a, list[blockIdx.x], fl[0], (int)threadIdx.x);
-        return;
-    }
-    const int gl = lp::GroupPar<G>::lane(), grp = (int)(threadIdx.x / G);
-    for (uint32_t t0 = blockIdx.x * NG; t0 < n; t0 += gridDim.x * NG) {
-        const uint32_t t = t0 + (uint32_t)grp;
-        if (t < n) keyed_fix_block<B, lp::GroupPar<G>, G, MAP>(a, list[t], fl[grp], gl);
-    }
+    fixup_walk<B, FixLdsS<B>>(list, count, [&](auto par, uint32_t id, FixLdsS<B> &f, int gl) {
+        keyed_fix_block<B, typename decltype(par)::Par, decltype(par)::G, MAP>(a, id, f, gl);
+    });
 }
 
 template <int B>
@@ -60,22 +49,19 @@ __global__ __launch_bounds__(64) void extract_keyed_fixup_kernel(KeyedArgs a, co
     keyed_fixup<B, false>(a, list, count);
 }
 
-#define TMF_CAT_(a, b) a##b
-#define TMF_CAT(a, b) TMF_CAT_(a, b)
-
-hipError_t TMF_CAT(launch_sigma1_fixup_, TMF_KEYED_B)(const KeyedArgs &a, const uint32_t *list, const uint32_t *count,
-                                                      int64_t max_entries, hipStream_t st)
+template <int B>
+hipError_t sigma1_fixup_b(const KeyedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st)
 {
-    hipLaunchKernelGGL((sigma1_fixup_kernel<TMF_KEYED_B>), dim3(fixup_grid<TMF_KEYED_B>(max_entries)), dim3(64), 0, st, a, list, count);
-    return hipGetLastError();
+    return launch_fixup<B>(sigma1_fixup_kernel<B>, a, list, count, max_entries, st);
 }
 
-hipError_t TMF_CAT(launch_extract_keyed_fixup_, TMF_KEYED_B)(const KeyedArgs &a, const uint32_t *list, const uint32_t *count,
-                                                             int64_t max_entries, hipStream_t st)
+template <int B>
+hipError_t extract_keyed_fixup_b(const KeyedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st)
 {
-    hipLaunchKernelGGL((extract_keyed_fixup_kernel<TMF_KEYED_B>), dim3(fixup_grid<TMF_KEYED_B>(max_entries)), dim3(64), 0, st, a, list,
-                       count);
-    return hipGetLastError();
+    return launch_fixup<B>(extract_keyed_fixup_kernel<B>, a, list, count, max_entries, st);
 }
+
+template hipError_t sigma1_fixup_b<TMF_B>(const KeyedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
+template hipError_t extract_keyed_fixup_b<TMF_B>(const KeyedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
 
 }  // namespace tmf

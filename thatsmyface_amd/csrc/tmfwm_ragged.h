@@ -49,6 +49,16 @@ hipError_t launch_embed_ragged_fixup(const RaggedArgs &r, const uint32_t *list, 
                                      hipStream_t st);
 hipError_t launch_extract_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
                                        hipStream_t st);
+// the four launchers per block size B: defined and instantiated for B = TMF_B in the size's own
+// translation units (tmfwm_ragged_strip.hip, tmfwm_ragged_fixup.hip), which alone see the kernels
+template <int B>
+hipError_t embed_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st);
+template <int B>
+hipError_t extract_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st);
+template <int B>
+hipError_t embed_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
+template <int B>
+hipError_t extract_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
 
 #if defined(__HIPCC__)
 // The table through the constant address space: a load from it at a wave-uniform address is a

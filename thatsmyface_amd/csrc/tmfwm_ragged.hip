@@ -5,36 +5,9 @@
 
 namespace tmf {
 
-#define TMF_RAGGED_DECL(B)                                                                                                   \
-    hipError_t launch_embed_ragged_##B(const RaggedArgs &, unsigned, hipStream_t);                                           \
-    hipError_t launch_extract_ragged_##B(const RaggedArgs &, unsigned, hipStream_t);                                         \
-    hipError_t launch_embed_ragged_fixup_##B(const RaggedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);  \
-    hipError_t launch_extract_ragged_fixup_##B(const RaggedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
-TMF_RAGGED_DECL(4)
-TMF_RAGGED_DECL(6)
-TMF_RAGGED_DECL(8)
-TMF_RAGGED_DECL(10)
-TMF_RAGGED_DECL(12)
-TMF_RAGGED_DECL(14)
-TMF_RAGGED_DECL(16)
-
-#define TMF_RAGGED_SWITCH(block, call)    \
-    switch (block) {                      \
-    case 4: return call(4);               \
-    case 6: return call(6);               \
-    case 8: return call(8);               \
-    case 10: return call(10);             \
-    case 12: return call(12);             \
-    case 14: return call(14);             \
-    case 16: return call(16);             \
-    default: return hipErrorInvalidValue; \
-    }
-
 int ragged_strip_blocks(int block)
 {
-#define TMF_BPW(B) Geo<B>::BPW
-    TMF_RAGGED_SWITCH(block, TMF_BPW)
-#undef TMF_BPW
+    return block_value(block, 1, [](auto b) { return (int)Geo<b()>::BPW; });  // (the callers have checked the size)
 }
 
 // a launch is one workgroup per strip wave: the caller's chunks keep it inside the grid limit
@@ -43,33 +16,25 @@ constexpr int64_t kGridMax = 0x7FFFFFFF;
 hipError_t launch_embed_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st)
 {
     if (waves <= 0 || waves > kGridMax) return hipErrorInvalidValue;
-#define TMF_CALL(B) launch_embed_ragged_##B(r, (unsigned)waves, st)
-    TMF_RAGGED_SWITCH(r.block, TMF_CALL)
-#undef TMF_CALL
+    return for_block(r.block, [&](auto b) { return embed_ragged_b<b()>(r, (unsigned)waves, st); });
 }
 
 hipError_t launch_extract_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st)
 {
     if (waves <= 0 || waves > kGridMax) return hipErrorInvalidValue;
-#define TMF_CALL(B) launch_extract_ragged_##B(r, (unsigned)waves, st)
-    TMF_RAGGED_SWITCH(r.block, TMF_CALL)
-#undef TMF_CALL
+    return for_block(r.block, [&](auto b) { return extract_ragged_b<b()>(r, (unsigned)waves, st); });
 }
 
 hipError_t launch_embed_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
                                      hipStream_t st)
 {
-#define TMF_CALL(B) launch_embed_ragged_fixup_##B(r, list, count, max_entries, st)
-    TMF_RAGGED_SWITCH(r.block, TMF_CALL)
-#undef TMF_CALL
+    return for_block(r.block, [&](auto b) { return embed_ragged_fixup_b<b()>(r, list, count, max_entries, st); });
 }
 
 hipError_t launch_extract_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
                                        hipStream_t st)
 {
-#define TMF_CALL(B) launch_extract_ragged_fixup_##B(r, list, count, max_entries, st)
-    TMF_RAGGED_SWITCH(r.block, TMF_CALL)
-#undef TMF_CALL
+    return for_block(r.block, [&](auto b) { return extract_ragged_fixup_b<b()>(r, list, count, max_entries, st); });
 }
 
 // The edge pixels of every frame of the chunk on one flat index over the table's edge prefix;

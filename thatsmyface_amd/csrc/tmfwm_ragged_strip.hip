@@ -1,4 +1,4 @@
-// Strip passes of the ragged calls (tmfwm_ragged.h) for one block size, TMF_RAGGED_B: the
+// Strip passes of the ragged calls (tmfwm_ragged.h) for one block size, TMF_B: the
 // Makefile compiles this file once per size (tmfwm_ragged_strip<b>.o), b = 8 under the same
 // max-ILP scheduler as its single-size sibling embed_kernel<8> (tmfwm_embed8.hip).
 //
@@ -9,8 +9,8 @@
 #include "tmfwm_passes.h"
 #include "tmfwm_ragged.h"
 
-#ifndef TMF_RAGGED_B
-#error "TMF_RAGGED_B: the block size of this translation unit"
+#ifndef TMF_B
+#error "TMF_B: the block size of this translation unit"
 #endif
 
 namespace tmf {
@@ -69,19 +69,21 @@ __global__ __launch_bounds__(64, (B > 8 ? 2 : kExtract8Waves)) void extract_ragg
     a.out[(int64_t)pos.bi * a.nbw + pos.bj] = extract_byte(sw, so, a.alpha32);
 }
 
-#define TMF_CAT_(a, b) a##b
-#define TMF_CAT(a, b) TMF_CAT_(a, b)
-
-hipError_t TMF_CAT(launch_embed_ragged_, TMF_RAGGED_B)(const RaggedArgs &r, unsigned waves, hipStream_t st)
+template <int B>
+hipError_t embed_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st)
 {
-    hipLaunchKernelGGL((embed_ragged_kernel<TMF_RAGGED_B>), dim3(waves), dim3(64), 0, st, r);
+    hipLaunchKernelGGL((embed_ragged_kernel<B>), dim3(waves), dim3(64), 0, st, r);
     return hipGetLastError();
 }
 
-hipError_t TMF_CAT(launch_extract_ragged_, TMF_RAGGED_B)(const RaggedArgs &r, unsigned waves, hipStream_t st)
+template <int B>
+hipError_t extract_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st)
 {
-    hipLaunchKernelGGL((extract_ragged_kernel<TMF_RAGGED_B>), dim3(waves), dim3(64), 0, st, r);
+    hipLaunchKernelGGL((extract_ragged_kernel<B>), dim3(waves), dim3(64), 0, st, r);
     return hipGetLastError();
 }
+
+template hipError_t embed_ragged_b<TMF_B>(const RaggedArgs &, unsigned, hipStream_t);
+template hipError_t extract_ragged_b<TMF_B>(const RaggedArgs &, unsigned, hipStream_t);
 
 }  // namespace tmf

@@ -293,27 +293,6 @@ __global__ __launch_bounds__(64, B <= 8 ? 3 : 2) void embed_rank1_kernel(EmbedAr
     }
 }
 
-template <int B>
-static hipError_t launch_rank1_b(EmbedArgs a, hipStream_t st)
-{
-    a.strips_per_row = (a.nbw + Geo<B>::BPW - 1) / Geo<B>::BPW;
-    const int64_t gx = (int64_t)a.strips_per_row * a.nbh;
-    for (int64_t f0 = 0; f0 < a.nframes; f0 += 65535) {
-        EmbedArgs c = a;
-        const int64_t nf = a.nframes - f0 < 65535 ? a.nframes - f0 : 65535;
-        c.src = a.src + f0 * a.frame_stride;
-        c.dst = a.dst + f0 * a.frame_stride;
-        c.wm = a.wm + f0 * a.wm_stride;
-        hipLaunchKernelGGL((embed_rank1_kernel<B>), dim3((unsigned)gx, (unsigned)nf), dim3(64), 0, st, c);
-    }
-    if (a.slow_list) {  // TMFWM_ROUTE_RANK1: the list pass over the blocks the pre-pass left
-        const int64_t rows = a.nframes * a.nbh;
-        const unsigned grid = (unsigned)(rows < (int64_t)kListShards ? rows : (int64_t)kListShards);
-        hipLaunchKernelGGL((embed_kernel<B, true>), dim3(grid), dim3(64), 0, st, a);
-    }
-    return hipGetLastError();
-}
-
 bool rank1_block(int block) { return block >= 4 && block <= 16 && block % 2 == 0; }
 
 // The rank-1 pre-pass over every block (every slider size, b = 4..16 even), then the edge pixels.  TMFWM_ROUTE_RANK1
@@ -324,16 +303,10 @@ hipError_t launch_embed_rank1(EmbedArgs a, hipStream_t st)
 {
     if (!rank1_block(a.block)) return hipErrorInvalidValue;
     if (a.nbh > 0 && a.nbw > 0) {
-        hipError_t e = hipErrorInvalidValue;
-        switch (a.block) {
-        case 4: e = launch_rank1_b<4>(a, st); break;
-        case 6: e = launch_rank1_b<6>(a, st); break;
-        case 8: e = launch_rank1_b<8>(a, st); break;
-        case 10: e = launch_rank1_b<10>(a, st); break;
-        case 12: e = launch_rank1_b<12>(a, st); break;
-        case 14: e = launch_rank1_b<14>(a, st); break;
-        case 16: e = launch_rank1_b<16>(a, st); break;
-        }
+        // TMFWM_ROUTE_RANK1: the list pass over the blocks the pre-pass left
+        const hipError_t e = for_block(a.block, [&](auto b) {
+            return launch_strips(a, Geo<b()>::BPW, embed_rank1_kernel<b()>, embed_kernel<b(), true>, st);
+        });
         if (e != hipSuccess) return e;
     }
     return launch_edges(a.src, a.dst, a.nframes, a.H, a.W, a.frame_stride, a.block, st);

@@ -48,7 +48,11 @@ if [ "${FALLBACK:-0}" = "1" ]; then
   FB="$T/fb.o"
   /opt/rocm/bin/hipcc $F -c "$K/tmfwm_fallback.hip" -o "$T/fb.o" &
   for b in 4 6 8 10 12 14 16; do
-    /opt/rocm/bin/hipcc $F -c "$K/tmfwm_fixup$b.hip" -o "$T/fx$b.o" &
+    if [ -f "$K/tmfwm_fixup.hip" ]; then  # (an older SRC_REV: one source file per size)
+      /opt/rocm/bin/hipcc $F -DTMF_B=$b -c "$K/tmfwm_fixup.hip" -o "$T/fx$b.o" &
+    else
+      /opt/rocm/bin/hipcc $F -c "$K/tmfwm_fixup$b.hip" -o "$T/fx$b.o" &
+    fi
     FB="$FB $T/fx$b.o"
   done
 fi

@@ -17,8 +17,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
          "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-o", "/dev/null", "-c"]
 ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 SIZES = (4, 6, 8, 10, 12, 14, 16)
-# compiled once per block size, with the block size in this macro
-PER_SIZE = {"tmfwm_ragged_strip.hip": "TMF_RAGGED_B", "tmfwm_ragged_fixup.hip": "TMF_RAGGED_B", "tmfwm_keyed_fixup.hip": "TMF_KEYED_B"}
+# compiled once per block size with -DTMF_B=<b> (the Makefile's PER_SIZE)
+PER_SIZE = ("tmfwm_fixup.hip", "tmfwm_ragged_fixup.hip", "tmfwm_keyed_fixup.hip", "tmfwm_ragged_strip.hip")
 KEYS = ["TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill",
         "LDS Size [bytes/block]"]
 
@@ -28,7 +28,7 @@ def units(csrc):
     for path in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
         tu = os.path.basename(path)
         if tu in PER_SIZE:
-            out += [(tu, ["-D%s=%d" % (PER_SIZE[tu], b)] + (ILP if (tu, b) == ("tmfwm_ragged_strip.hip", 8) else [])) for b in SIZES]
+            out += [(tu, ["-DTMF_B=%d" % b] + (ILP if (tu, b) == ("tmfwm_ragged_strip.hip", 8) else [])) for b in SIZES]
         else:
             out.append((tu, ILP if tu == "tmfwm_embed8.hip" else []))
     return out + [("tmfwm_capi.cpp", ["-x", "hip"]), ("tmfwm_multi.cpp", ["-x", "hip"])]
