@@ -409,6 +409,35 @@ int tmfwm_prepare_tiles(const uint8_t *wm, int64_t n_wm, int32_t wm_height, int3
                         int32_t mem_kind, void *hip_stream);
 
 /*
+ * Ragged tile preparation (added within ABI 10; the version number is unchanged and the two calls
+ * above keep their behaviour, their synchronisation included): n_jobs jobs, each with its own
+ * watermark and its own tile, both of any size, resampled by one set of launches.  Every tile's
+ * bytes are tmfwm_prepare_tile's for that job alone; preserve_ratio is one flag for the call.
+ *
+ * The descriptor array is host memory whatever mem_kind says about the pointers inside it, and
+ * the library copies it before it returns.  Each distinct (input size, output size) resample axis
+ * of the call is built once and shared by the jobs and the two directions that use it; all tables
+ * and the job table go to the device in one copy.  TMFWM_MEM_DEVICE: the call enqueues on
+ * `hip_stream` and returns without synchronising; every `tile` must be disjoint from every `wm`
+ * of the call and from every other `tile` (TMFWM_ERR_INVALID otherwise), while watermarks may
+ * share memory (one watermark for many sizes).  TMFWM_MEM_HOST: watermarks and tiles are staged,
+ * the tiles copied back, and the call returns when they have landed.
+ *
+ * All arguments are checked before the device is touched, no job is skipped, and nothing is
+ * written when a job is refused: a size <= 0 or an empty resized size under preserve_ratio
+ * ("job i" in the message; tmfwm_prepare_tile refuses the same inputs) and a NULL pointer return
+ * TMFWM_ERR_INVALID.  n_jobs == 0 does nothing.
+ */
+typedef struct {
+    const uint8_t *wm;    /* wm_height x wm_width grey bytes, packed rows */
+    uint8_t *tile;        /* tile_height x tile_width, packed */
+    int32_t wm_height, wm_width, tile_height, tile_width;
+} tmfwm_tile_job;         /* 32 bytes */
+
+int tmfwm_prepare_tiles_ragged(const tmfwm_tile_job *jobs, int64_t n_jobs, int32_t preserve_ratio, int32_t mem_kind,
+                               void *hip_stream);
+
+/*
  * The watermark's payload, host-side C++ (no GPU, no torch): the QR codec
  * and AES-CBC the app wraps around embed / extract.  The reference builds the watermark with
  * modules/encryption.py:8-40 (encrypt_watermark: random 16-byte IV + AES-CBC of the

@@ -74,6 +74,13 @@ class ExtractFrame(ctypes.Structure):
                 ("height", ctypes.c_int32), ("width", ctypes.c_int32)]
 
 
+class TileJob(ctypes.Structure):
+    """tmfwm_tile_job: one job of tmfwm_prepare_tiles_ragged (include/tmfwm.h)."""
+
+    _fields_ = [("wm", ctypes.c_void_p), ("tile", ctypes.c_void_p), ("wm_height", ctypes.c_int32), ("wm_width", ctypes.c_int32),
+                ("tile_height", ctypes.c_int32), ("tile_width", ctypes.c_int32)]
+
+
 # name -> (restype, argtypes): exactly the entry points of include/tmfwm.h
 SIGNATURES = {
     "tmfwm_abi_version": (ctypes.c_int, []),
@@ -111,6 +118,7 @@ SIGNATURES = {
     "tmfwm_synth_frames": (ctypes.c_int, [ctypes.c_uint64, _I64, _I64, _I64, _VP, _VP]),
     "tmfwm_prepare_tile": (ctypes.c_int, [_VP, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _VP]),
     "tmfwm_prepare_tiles": (ctypes.c_int, [_VP, _I64, _I32, _I32, _I64, _I32, _I32, _I32, _VP, _I64, _I32, _VP]),
+    "tmfwm_prepare_tiles_ragged": (ctypes.c_int, [_VP, _I64, _I32, _I32, _VP]),
     "tmfwm_qr_encode": (ctypes.c_int, [_VP, _I32, _I32, _I32, _I32, _VP, _I32, _VP]),
     "tmfwm_qr_decode": (ctypes.c_int, [_VP, _I32, _I32, _I64, _VP, _I32, _VP]),
     "tmfwm_qr_decode_batch": (ctypes.c_int, [_VP, _I64, _I32, _I32, _VP, _I32, _VP]),

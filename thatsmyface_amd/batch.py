@@ -435,3 +435,51 @@ def prepare_tiles(watermarks_l: torch.Tensor, tile_height: int, tile_width: int,
                                          int(bool(preserve_ratio)), out.data_ptr(), tile_height * tile_width, _lib.MEM_DEVICE,
                                          _stream(stream)), "prepare_tiles")
     return out
+
+
+def prepare_tiles_ragged(watermarks, sizes, preserve_ratio: bool = False, out=None, stream=None) -> list:
+    """prepare_tile for jobs of mixed sizes by one set of launches (tmfwm_prepare_tiles_ragged):
+    watermarks is a list of contiguous (h, w) uint8 GPU tensors, one per entry of sizes, or a single tensor
+    used for every size; sizes is a list of (tile_height, tile_width).  Returns one
+    (tile_height, tile_width) tile per job, views of one device allocation (or `out`, a list of
+    contiguous tensors of those shapes on the watermarks' device); tile i is the bytes of
+    prepare_tile(watermarks[i], *sizes[i], preserve_ratio).  Each distinct resample axis of the
+    call is built once and everything goes up in one copy; the call does not synchronise."""
+    import ctypes
+
+    sizes = [(int(th), int(tw)) for th, tw in sizes]
+    if isinstance(watermarks, torch.Tensor):
+        watermarks = [watermarks] * len(sizes)
+    watermarks = list(watermarks)
+    if len(watermarks) != len(sizes):
+        raise ValueError(f"{len(watermarks)} watermarks for {len(sizes)} sizes")
+    dev = None
+    for i, w in enumerate(watermarks):
+        if not isinstance(w, torch.Tensor) or not w.is_cuda or w.dtype != torch.uint8 or w.dim() != 2 or not w.is_contiguous():
+            raise ValueError(f"watermarks[{i}] must be a contiguous (h, w) uint8 GPU tensor")
+        dev = w.device if dev is None else dev
+        if w.device != dev:
+            raise ValueError(f"watermarks[{i}] is on {w.device}, the call's other tensors on {dev}")
+    for i, (th, tw) in enumerate(sizes):
+        if th <= 0 or tw <= 0:
+            raise ValueError(f"sizes[{i}] = {(th, tw)}: height and width must be > 0")
+    if not sizes:
+        return []
+    if out is None:
+        out = _ragged_views([th * tw for th, tw in sizes], lambda i: sizes[i], dev)
+    else:
+        out = list(out)
+        if len(out) != len(sizes):
+            raise ValueError("out must hold one tile per job")
+        for i, t in enumerate(out):
+            if (not isinstance(t, torch.Tensor) or tuple(t.shape) != sizes[i] or t.dtype != torch.uint8 or t.device != dev
+                    or not t.is_contiguous()):
+                raise ValueError(f"out[{i}] must be a contiguous {sizes[i]} uint8 tensor on {dev}")
+    desc = (_lib.TileJob * len(sizes))()
+    for i, (w, t) in enumerate(zip(watermarks, out)):
+        desc[i] = _lib.TileJob(w.data_ptr(), t.data_ptr(), w.shape[0], w.shape[1], sizes[i][0], sizes[i][1])
+    with torch.cuda.device(dev):
+        L = _lib.load()
+        _lib.check(L.tmfwm_prepare_tiles_ragged(ctypes.addressof(desc), len(sizes), int(bool(preserve_ratio)), _lib.MEM_DEVICE,
+                                                _stream(stream)), "prepare_tiles_ragged")
+    return list(out)

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -1408,16 +1409,16 @@ struct Span {
     int64_t frame;
 };
 
-int check_ragged_overlap(std::vector<Span> &spans)
+int check_ragged_overlap(std::vector<Span> &spans, const char *unit = "frame")  // unit: what Span::frame counts
 {
     std::sort(spans.begin(), spans.end(), [](const Span &a, const Span &b) { return a.lo < b.lo; });
     uintptr_t in_hi = 0, out_hi = 0;
     int64_t in_f = -1, out_f = -1;
     for (const Span &s : spans) {
         if (s.lo == s.hi) continue;
-        if (s.out && s.lo < in_hi) return fail(TMFWM_ERR_INVALID, "frame %lld's output overlaps an input of frame %lld", (long long)s.frame, (long long)in_f);
-        if (s.out && s.lo < out_hi) return fail(TMFWM_ERR_INVALID, "frame %lld's output overlaps frame %lld's", (long long)s.frame, (long long)out_f);
-        if (!s.out && s.lo < out_hi) return fail(TMFWM_ERR_INVALID, "frame %lld's output overlaps an input of frame %lld", (long long)out_f, (long long)s.frame);
+        if (s.out && s.lo < in_hi) return fail(TMFWM_ERR_INVALID, "%s %lld's output overlaps an input of %s %lld", unit, (long long)s.frame, unit, (long long)in_f);
+        if (s.out && s.lo < out_hi) return fail(TMFWM_ERR_INVALID, "%s %lld's output overlaps %s %lld's", unit, (long long)s.frame, unit, (long long)out_f);
+        if (!s.out && s.lo < out_hi) return fail(TMFWM_ERR_INVALID, "%s %lld's output overlaps an input of %s %lld", unit, (long long)out_f, unit, (long long)s.frame);
         if (s.out && s.hi > out_hi) out_hi = s.hi, out_f = s.frame;
         if (!s.out && s.hi > in_hi) in_hi = s.hi, in_f = s.frame;
     }
@@ -1651,6 +1652,109 @@ int ragged_call(std::vector<RFrame> &fr, int32_t block, double alpha, bool extra
     return hc.finish();
 }
 
+// ---- ragged tile preparation (tmfwm_tile_plan.h)
+
+// TMFWM_DEBUG_TILE_SCRATCH (bytes) lowers the bound of a group's scratch so that the tests can
+// run several groups at small sizes
+int64_t tile_scratch_cap()
+{
+    const char *e = std::getenv("TMFWM_DEBUG_TILE_SCRATCH");
+    if (!e || !*e) return tmf::kTileScratchCap;
+    const long long v = std::atoll(e);
+    return v > 0 && v < tmf::kTileScratchCap ? (int64_t)v : tmf::kTileScratchCap;
+}
+
+// The plan's job table and packed tables built in one pinned buffer, uploaded in one copy, then
+// two launches per group (one where no job of the group needs the horizontal pass).  Nothing here
+// waits for the stream.
+int run_tiles_ragged(const tmf::TilePlan &plan, hipStream_t st)
+{
+    const size_t jbytes = plan.jobs.size() * sizeof(tmf::TileJob), tbytes = plan.tables.size() * sizeof(int);
+    TableSlot slot;
+    if (int rc = take_table(jbytes + tbytes, stream_device(st), slot)) return rc;
+    std::copy(plan.jobs.begin(), plan.jobs.end(), static_cast<tmf::TileJob *>(slot.p));
+    std::copy(plan.tables.begin(), plan.tables.end(), reinterpret_cast<int *>(static_cast<uint8_t *>(slot.p) + jbytes));
+    DevBuf dtab, dtmp;
+    int rc = dtab.alloc(jbytes + tbytes, st, "tile jobs and resample tables");
+    if (rc == 0 && hipMemcpyAsync(dtab.p, slot.p, jbytes + tbytes, hipMemcpyHostToDevice, st) != hipSuccess)
+        rc = fail(TMFWM_ERR_HIP, "copying the tile jobs and resample tables failed: %s", hipGetErrorString(hipGetLastError()));
+    give_table(slot, st);
+    if (rc) return rc;
+    if (int rc2 = dtmp.alloc((size_t)plan.scratch, st, "resample scratch")) return rc2;
+    const tmf::TileJob *djobs = static_cast<const tmf::TileJob *>(dtab.p);
+    const int *dtables = reinterpret_cast<const int *>(static_cast<const uint8_t *>(dtab.p) + jbytes);
+    for (const tmf::TileGroup &g : plan.groups)  // in stream order: the groups share the scratch
+        TMF_HIP(tmf::launch_tiles_ragged(djobs + g.first, g.n, dtables, static_cast<uint8_t *>(dtmp.p), g.h_items, g.v_items, st));
+    return 0;
+}
+
+int tiles_ragged_call(std::vector<tmf::TileJobIn> &jobs, bool preserve_ratio, int32_t mem_kind, void *hip_stream)
+{
+    // sizes, the resized size and the pointers of every job, before the device is touched
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        const tmf::TileJobIn &j = jobs[i];
+        tmf::TileGeom geo;
+        if (j.wh <= 0 || j.ww <= 0 || j.th <= 0 || j.tw <= 0)
+            return fail(TMFWM_ERR_INVALID, "job %zu: height and width must be > 0 (watermark %dx%d, tile %dx%d)", i, j.ww, j.wh, j.tw,
+                        j.th);
+        if (!tmf::tile_geom(j.wh, j.ww, j.th, j.tw, preserve_ratio, geo))
+            return fail(TMFWM_ERR_INVALID, "job %zu: height and width must be > 0 (resized %dx%d)", i, geo.rw, geo.rh);
+        if (!j.wm || !j.tile) return fail(TMFWM_ERR_INVALID, "job %zu: NULL pointer in the descriptor", i);
+    }
+    if (int rc = need_device()) return rc;
+    if (jobs.empty()) return 0;
+    hipStream_t st = pick_stream(hip_stream);
+    DevBuf stage;
+    std::vector<uint8_t *> host_tile;
+    if (mem_kind == TMFWM_MEM_DEVICE) {
+        std::vector<Span> spans;
+        spans.reserve(jobs.size() * 2);
+        for (size_t i = 0; i < jobs.size(); ++i) {
+            const tmf::TileJobIn &j = jobs[i];
+            if (int rc = check_device_ptr(j.wm, "wm")) return fail(rc, "job %zu: %s", i, t_err.c_str());
+            if (int rc = check_device_ptr(j.tile, "tile")) return fail(rc, "job %zu: %s", i, t_err.c_str());
+            const uintptr_t w = reinterpret_cast<uintptr_t>(j.wm), t = reinterpret_cast<uintptr_t>(j.tile);
+            spans.push_back({w, w + (uintptr_t)j.wh * (uintptr_t)j.ww, false, (int64_t)i});
+            spans.push_back({t, t + (uintptr_t)j.th * (uintptr_t)j.tw, true, (int64_t)i});
+        }
+        if (int rc = check_ragged_overlap(spans, "job")) return rc;
+    } else {  // host memory: every watermark and tile staged compactly in one device allocation (16-byte aligned pieces)
+        size_t total = 0;
+        std::vector<size_t> off(jobs.size() * 2);
+        for (size_t i = 0; i < jobs.size(); ++i) {
+            off[2 * i] = total;
+            total += round16((size_t)jobs[i].wh * (size_t)jobs[i].ww);
+            off[2 * i + 1] = total;
+            total += round16((size_t)jobs[i].th * (size_t)jobs[i].tw);
+        }
+        if (int rc = stage.alloc(total, st, "watermarks and tiles")) return rc;
+        uint8_t *base = static_cast<uint8_t *>(stage.p);
+        host_tile.resize(jobs.size());
+        for (size_t i = 0; i < jobs.size(); ++i) {
+            TMF_HIP(hipMemcpyAsync(base + off[2 * i], jobs[i].wm, (size_t)jobs[i].wh * (size_t)jobs[i].ww, hipMemcpyHostToDevice, st));
+            host_tile[i] = jobs[i].tile;
+            jobs[i].wm = base + off[2 * i];
+            jobs[i].tile = base + off[2 * i + 1];
+        }
+    }
+    tmf::TilePlan plan;
+    const char *why = "";
+    int64_t bad = -1;
+    try {
+        bad = plan.build(jobs.data(), (int64_t)jobs.size(), preserve_ratio, tile_scratch_cap(), &why);
+    } catch (const std::bad_alloc &) {
+        return fail(TMFWM_ERR_NOMEM, "host allocation for the resample tables failed");
+    }
+    if (bad >= 0) return fail(TMFWM_ERR_INVALID, "job %lld: %s", (long long)bad, why);
+    if (int rc = run_tiles_ragged(plan, st)) return rc;
+    if (mem_kind == TMFWM_MEM_HOST) {
+        for (size_t i = 0; i < jobs.size(); ++i)
+            TMF_HIP(hipMemcpyAsync(host_tile[i], jobs[i].tile, (size_t)jobs[i].th * (size_t)jobs[i].tw, hipMemcpyDeviceToHost, st));
+        TMF_HIP(hipStreamSynchronize(st));  // the tiles have landed
+    }
+    return 0;
+}
+
 }  // namespace
 }  // extern "C++"
 
@@ -1671,6 +1775,19 @@ int tmfwm_extract_ragged(const tmfwm_extract_frame *frames, int64_t n_frames, in
     for (int64_t i = 0; i < n_frames; ++i)
         fr[(size_t)i] = {frames[i].wm_rgb, frames[i].orig_rgb, frames[i].out_tile, frames[i].height, frames[i].width};
     return ragged_call(fr, block, alpha, true, mem_kind, hip_stream, route, n_lapack_blocks);
+}
+
+int tmfwm_prepare_tiles_ragged(const tmfwm_tile_job *jobs, int64_t n_jobs, int32_t preserve_ratio, int32_t mem_kind,
+                               void *hip_stream)
+{
+    t_err.clear();
+    if (n_jobs < 0) return fail(TMFWM_ERR_INVALID, "negative size (n_jobs=%lld)", (long long)n_jobs);
+    if (n_jobs > 0 && !jobs) return fail(TMFWM_ERR_INVALID, "jobs is NULL");
+    if (mem_kind != TMFWM_MEM_HOST && mem_kind != TMFWM_MEM_DEVICE) return fail(TMFWM_ERR_INVALID, "mem_kind %d", mem_kind);
+    std::vector<tmf::TileJobIn> in((size_t)n_jobs);  // the library's copy: the caller's array is not read again
+    for (int64_t i = 0; i < n_jobs; ++i)
+        in[(size_t)i] = {jobs[i].wm, jobs[i].tile, jobs[i].wm_height, jobs[i].wm_width, jobs[i].tile_height, jobs[i].tile_width};
+    return tiles_ragged_call(in, preserve_ratio != 0, mem_kind, hip_stream);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 
 #include "../../include/tmfwm.h"
 #include "tmfwm_sizes.h"
+#include "tmfwm_tile_plan.h"
 
 namespace tmf {
 
@@ -190,14 +191,8 @@ hipError_t launch_lapack_svd_blocks(const float *D, int64_t nb, int block, float
                                     hipStream_t st);
 hipError_t launch_lapack_nrm2(const double *x, int64_t nvec, int n, int inc, double *out, hipStream_t st);
 hipError_t launch_svd_blocks(const float *D, int64_t nb, int block, float *U, float *S, float *Vt, int32_t *sweeps, hipStream_t st);
-// Watermark-tile preparation (tmfwm_tile.hip): Pillow's LANCZOS resample tables.
-struct ResampleAxis {
-    int ksize = 0;
-    std::vector<int> bounds;  // 2 per output sample: first input index, count
-    std::vector<int> kk;      // ksize 22-bit fixed-point taps per output sample
-    void build(int in_size, int out_size);
-};
-
+// Watermark-tile preparation (tmfwm_tile.hip): Pillow's LANCZOS resample tables (ResampleAxis:
+// tmfwm_tile_plan.h).
 struct ResamplePlan {
     int ih = 0, iw = 0, oh = 0, ow = 0, y_first = 0, y_last = 0;
     bool need_h = false, need_v = false;
@@ -216,6 +211,10 @@ constexpr int64_t kResizeGroup = 1024;  // images per launch
 size_t resize_tmp_bytes(const ResamplePlan &plan, int64_t n);
 hipError_t launch_resize_lanczos_batch(const uint8_t *in, int64_t in_stride, int64_t n, const ResamplePlan &plan, const int *tables,
                                        uint8_t *tmp, uint8_t *out, int ldo, int64_t out_stride, hipStream_t st);
+// One group of a ragged call (tmfwm_tile_plan.h): jobs [0, n) of the group in device memory, the
+// call's packed tables, the shared scratch; the horizontal launch only where h_items > 0.
+hipError_t launch_tiles_ragged(const TileJob *jobs, int64_t n, const int *tables, uint8_t *scratch, int64_t h_items,
+                               int64_t v_items, hipStream_t st);
 hipError_t launch_synth(uint64_t seed, int64_t frame0, int64_t nframes, int64_t frame_bytes, uint8_t *out, hipStream_t st);
 
 }  // namespace tmf

@@ -16,66 +16,9 @@
 #include <vector>
 
 #include "tmfwm_internal.h"
+#include "tmfwm_ragged.h"  // TMF_CONST_AS
 
 namespace tmf {
-
-namespace {
-
-constexpr int kPrecisionBits = 32 - 8 - 2;
-
-double sinc(double x)
-{
-    if (x == 0.0) return 1.0;
-    x = x * 3.14159265358979323846;  // M_PI
-    return std::sin(x) / x;
-}
-
-double lanczos(double x) { return (-3.0 <= x && x < 3.0) ? sinc(x) * sinc(x / 3) : 0.0; }
-
-}  // namespace
-
-// Resample.c precompute_coeffs + normalize_coeffs_8bpc for box (0, in_size) -> out_size.
-void ResampleAxis::build(int in_size, int out_size)
-{
-    const float in0 = 0.0f, in1 = (float)in_size;
-    double filterscale, scale;
-    filterscale = scale = (double)(in1 - in0) / out_size;
-    if (filterscale < 1.0) filterscale = 1.0;
-    const double support = 3.0 * filterscale;
-    ksize = (int)std::ceil(support) * 2 + 1;
-    bounds.assign((size_t)out_size * 2, 0);
-    kk.assign((size_t)out_size * ksize, 0);
-    std::vector<double> k((size_t)ksize);
-    for (int xx = 0; xx < out_size; xx++) {
-        const double center = in0 + (xx + 0.5) * scale, ss = 1.0 / filterscale;
-        double ww = 0.0;
-        int xmin = (int)(center - support + 0.5);
-        if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + support + 0.5);
-        if (xmax > in_size) xmax = in_size;
-        xmax -= xmin;
-        int x;
-        for (x = 0; x < xmax; x++) {
-            const double w = lanczos((x + xmin - center + 0.5) * ss);
-            k[x] = w;
-            ww += w;
-        }
-        for (x = 0; x < xmax; x++)
-            if (ww != 0.0) k[x] /= ww;
-        for (; x < ksize; x++) k[x] = 0;
-        for (x = 0; x < ksize; x++)
-            kk[(size_t)xx * ksize + x] =
-                k[x] < 0 ? (int)(-0.5 + k[x] * (1 << kPrecisionBits)) : (int)(0.5 + k[x] * (1 << kPrecisionBits));
-        bounds[xx * 2] = xmin;
-        bounds[xx * 2 + 1] = xmax;
-    }
-}
-
-__device__ __forceinline__ uint8_t clip8(int v)
-{
-    v >>= kPrecisionBits;
-    return (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v);
-}
 
 // The three kernels take the image index from blockIdx.z: image i is read at in + i * istride
 // and written at out + i * ostride (one launch over a batch of equally sized images).
@@ -92,9 +35,7 @@ __global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t *__restri
     const int xmin = bounds[2 * xx], xmax = bounds[2 * xx + 1];
     const uint8_t *src = in + (int64_t)(yy + y0) * iw + xmin;
     const int *k = kk + (int64_t)xx * ks;
-    int ss = 1 << (kPrecisionBits - 1);
-    for (int x = 0; x < xmax; x++) ss += (int)src[x] * k[x];
-    out[(int64_t)yy * ldo + xx] = clip8(ss);
+    out[(int64_t)yy * ldo + xx] = resample_h_byte(src, k, xmax);
 }
 
 // out[yy][xx] = clip8(2^21 + sum_y in[ymin + y][xx] * k[yy][y])
@@ -108,9 +49,7 @@ __global__ __launch_bounds__(256) void resample_v_kernel(const uint8_t *__restri
     out += blockIdx.z * ostride;
     const int ymin = bounds[2 * yy], ymax = bounds[2 * yy + 1];
     const int *k = kk + (int64_t)yy * ks;
-    int ss = 1 << (kPrecisionBits - 1);
-    for (int y = 0; y < ymax; y++) ss += (int)in[(int64_t)(y + ymin) * iw + xx] * k[y];
-    out[(int64_t)yy * ldo + xx] = clip8(ss);
+    out[(int64_t)yy * ldo + xx] = resample_v_byte(in, iw, xx, ymin, k, ymax);
 }
 
 __global__ __launch_bounds__(256) void copy_rows_kernel(const uint8_t *__restrict__ in, int64_t istride, int iw, int rows,
@@ -118,6 +57,46 @@ __global__ __launch_bounds__(256) void copy_rows_kernel(const uint8_t *__restric
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x < iw && y < rows) out[blockIdx.z * ostride + (int64_t)y * ldo + x] = in[blockIdx.z * istride + (int64_t)y * iw + x];
+}
+
+// ---- the ragged call (tmfwm_prepare_tiles_ragged; the plan and the per-thread bodies: tmfwm_tile_plan.h)
+//
+// Both grids are flat: one workgroup of kTileSeg threads -- one wave -- per row segment of the
+// group's jobs.  The wave finds its job by binary search in the work-item prefix of the job table,
+// read through the constant address space: the job's fields are scalar loads and stay in SGPRs.
+
+// The intermediate rows [y_first, y_first + rows) x rw of every job with need_h, into the scratch.
+// The taps differ per thread (one output column each), so the tables are ordinary global loads.
+__global__ __launch_bounds__(kTileSeg) void resample_h_ragged_kernel(const TileJob *jobs, int n, const int *__restrict__ tables,
+                                                                     uint8_t *__restrict__ scratch)
+{
+    const TMF_CONST_AS TileJob *J = (const TMF_CONST_AS TileJob *)jobs;
+    const uint32_t item = blockIdx.x;
+    const int j = tile_find(n, item, [&](int i) { return J[i].h_item0; });
+    tile_h_thread(J + j, item - J[j].h_item0, (int)threadIdx.x, tables, scratch);
+}
+
+// Every byte of every tile: 255 outside the paste rectangle, the vertical taps (or a copy) inside.
+// Job and output row are the wave's, so a row's bounds and taps come through scalar loads too.
+__global__ __launch_bounds__(kTileSeg) void resample_v_paste_ragged_kernel(const TileJob *jobs, int n, const int *tables,
+                                                                           const uint8_t *scratch)
+{
+    const TMF_CONST_AS TileJob *J = (const TMF_CONST_AS TileJob *)jobs;
+    const uint32_t item = blockIdx.x;
+    const int j = tile_find(n, item, [&](int i) { return J[i].v_item0; });
+    tile_v_thread(J + j, item - J[j].v_item0, (int)threadIdx.x, (const TMF_CONST_AS int *)tables, scratch);
+}
+
+hipError_t launch_tiles_ragged(const TileJob *jobs, int64_t n, const int *tables, uint8_t *scratch, int64_t h_items,
+                               int64_t v_items, hipStream_t st)
+{
+    if (n <= 0 || n > 0x7FFFFFFFll || h_items > kTileItemCap || v_items > kTileItemCap) return hipErrorInvalidValue;
+    if (h_items > 0)
+        hipLaunchKernelGGL(resample_h_ragged_kernel, dim3((unsigned)h_items), dim3(kTileSeg), 0, st, jobs, (int)n, tables, scratch);
+    if (v_items > 0)
+        hipLaunchKernelGGL(resample_v_paste_ragged_kernel, dim3((unsigned)v_items), dim3(kTileSeg), 0, st, jobs, (int)n, tables,
+                           (const uint8_t *)scratch);
+    return hipGetLastError();
 }
 
 static dim3 grid3(int w, int h, int64_t n) { return dim3((unsigned)((w + 255) / 256), (unsigned)h, (unsigned)n); }

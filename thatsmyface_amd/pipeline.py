@@ -11,7 +11,8 @@ what is left.  This module overlaps the three stages:
   ``embed_batch`` (one launch) -> async D2H into pinned memory; the watermark tile
   for each image size is prepared once on the device (``tmfwm_prepare_tile``);
   with ``batch_images=K`` the stage takes up to K decoded images of any sizes at a time and
-  embeds the group with one ``embed_ragged`` (``RaggedGpuStage``);
+  prepares the group's tiles with one ``prepare_tiles_ragged`` and embeds the group with one
+  ``embed_ragged`` (``RaggedGpuStage``);
 * encode (thread pool): waits for the copy, PNG-encodes (zlib releases the GIL).
 
 Results come back in input order and are byte-identical to
@@ -117,34 +118,50 @@ class GpuStage:
 
 class RaggedGpuStage(GpuStage):
     """Batched device stage (``embed_images(..., batch_images=K)``): a group of decoded images of
-    any sizes is uploaded, each image's tile comes from GpuStage's cached ``prepare_tile``, one
-    ``embed_ragged`` embeds the whole group, and the results are copied back.
+    any sizes is uploaded, one ``prepare_tiles_ragged`` makes the tiles the group needs and the
+    cache does not hold, one ``embed_ragged`` embeds the whole group, and the results are copied
+    back.
 
     Called as ``stage(rgbs, indices)`` with the group's pixel arrays and their positions in the
     input (the watermark of image ``i`` is watermark ``i`` when there is one per image); returns
     one ``(pixels, wait)`` per image, in the group's order."""
 
+    def _group_tiles(self, keys):
+        """The tiles of a group's (watermark, nbh, nbw) keys: those the cache does not hold, each
+        once, from one ``prepare_tiles_ragged`` on the stage's stream (no synchronisation).  With
+        one watermark for all images a size's tile stays cached for later groups; with one
+        watermark per image a key is used once, so its tile lives only as long as the group."""
+        need = [k for k in dict.fromkeys(keys) if k not in self.tiles]
+        made = {}
+        if need:
+            made = dict(zip(need, self.batch.prepare_tiles_ragged([self.wm_grey[k[0]] for k in need], [k[1:] for k in need],
+                                                                  self.preserve_ratio, stream=self.stream)))
+            if not self.per_image:
+                self.tiles.update(made)
+        return [made[k] if k in made else self.tiles[k] for k in keys]
+
     def __call__(self, rgbs, indices):
         torch = self.torch
-        tiles, host_in, host_out = [], [], []
+        keys, host_in, host_out = [], [], []
         for rgb, index in zip(rgbs, indices):
             h, w = rgb.shape[:2]
             nbh, nbw = h // self.block, w // self.block
             if nbh == 0 or nbw == 0:
                 raise ValueError("height and width must be > 0")  # as GpuStage
-            tiles.append(self._tile(nbh, nbw, index if self.per_image else 0))
+            keys.append((index if self.per_image else 0, nbh, nbw))
             hi = torch.empty((h, w, 3), dtype=torch.uint8, pin_memory=True)
             hi.numpy()[...] = rgb
             host_in.append(hi)
             host_out.append(torch.empty((h, w, 3), dtype=torch.uint8, pin_memory=True))
         with torch.cuda.stream(self.stream):
+            tiles = self._group_tiles(keys)
             dev_in = [h.to(self.device, non_blocking=True) for h in host_in]
             dev_out = self.batch.embed_ragged(dev_in, tiles, self.block, self.alpha, stream=self.stream, route=self.route)
             for ho, do in zip(host_out, dev_out):
                 ho.copy_(do, non_blocking=True)
             done = torch.cuda.Event()
             done.record(self.stream)
-        keep = (dev_in, dev_out, host_in)  # alive until the copies have landed
+        keep = (dev_in, dev_out, host_in, tiles)  # alive until the copies have landed
 
         def wait(_e=done, _k=keep):
             _e.synchronize()
