@@ -45,6 +45,10 @@ extern template __global__ void embed_kernel<14, true>(EmbedArgs);
 extern template __global__ void embed_kernel<16, true>(EmbedArgs);
 
 constexpr int kRank1Iters = 4;  // f64 power steps before the a-posteriori test
+// LAPACK's two measured constants (tools/exp/lapack_bounds.py, profiles/r06/lapack_bounds_b*.json;
+// tests/test_rank1_bound.py holds them to tests/k_corpus.py's), in units of 2^-53 sigma_1:
+constexpr double kRank1ResidUnits = 8192.0;  // residual |U S V^T - D| per element: gamma' = 2^-40 s1
+constexpr double kRank1PairUnits = 1024.0;   // top pair, per element, over (s1 - s2)
 
 // value of element k (0 <= k < B) of a per-row quantity held as R rows per lane (lane k / R)
 template <int B, int L, int K>
@@ -165,7 +169,7 @@ __global__ __launch_bounds__(64, B <= 8 ? 3 : 2) void embed_rank1_kernel(EmbedAr
     const double s2hi = __builtin_sqrt(fhi - rlo > 0.0 ? fhi - rlo : 0.0) * (1.0 + 512.0 * u53);
     const double g1 = s1lo - s2hi;
     const double theta = rr0 / (gap > 0.0 ? gap : 1.0);
-    const double eps_uv = zero ? 0.0 : 1.01 * theta + 1024.0 * u53 * s1hi / (g1 > 0.0 ? g1 : 1.0) + 0x1p-45;
+    const double eps_uv = zero ? 0.0 : 1.01 * theta + kRank1PairUnits * u53 * s1hi / (g1 > 0.0 ? g1 : 1.0) + 0x1p-45;
     bool ok = zero || (gap > 0.0 && g1 > 0.0 && eps_uv <= 0x1p-30 && rho == rho);
 
     // the unit top pair: v / |v|, u = D v / |D v| (this lane's rows)
@@ -196,7 +200,8 @@ __global__ __launch_bounds__(64, B <= 8 ? 3 : 2) void embed_rank1_kernel(EmbedAr
     const float e = (float)eps_uv * (1.0f + 0x1p-20f);
     const float cabs = (float)__builtin_fabs(cw) * (1.0f + 0x1p-20f), s1f = (float)s1hi * (1.0f + 0x1p-20f);
     const float al = 1.01f * (B + 6) * u24, be = 1.01f * ((B + 6) * u24 * cabs + 2.0f * u24 * (s1f + cabs));
-    const float ga = 0x1p-40f * s1f + cabs * e * (2.0f + e);
+    constexpr float resid = (float)(kRank1ResidUnits * u53);  // 2^-40, exact
+    const float ga = resid * s1f + cabs * e * (2.0f + e);
     const float w1 = 2.0f * u24 * (1.0f + al), w2 = 2.0f * u24 * (cabs + be);  // 2 u m_1, 2 u m_2
     float ra[R], ru[R];  // a_i = |D_i,:|^(1/2), u'_i = |u_i| + e on this lane's rows
 #pragma unroll

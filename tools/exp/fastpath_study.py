@@ -37,8 +37,15 @@ import idct_bound as IB  # noqa: E402
 from lapack_path import _blocks, _unblocks, photo_cover  # noqa: E402
 from cert_study import lp_f64  # noqa: E402
 
+import k_corpus as KC  # noqa: E402
+
 U32 = 2.0**-24
 EPS = 2.0**-53
+# LAPACK's two measured constants of the rank-1 pre-pass, in units of 2^-53 s1 (the kernel's
+# kRank1ResidUnits / kRank1PairUnits, csrc/tmfwm_rank1.hip; tools/exp/lapack_bounds.py measures them)
+RESID_UNITS = KC.RESID_UNITS
+PAIR_UNITS = KC.PAIR_UNITS
+GATE_EPS_UV = 2.0**-30  # the pre-pass refuses a block whose top pair is known no better than this
 
 
 def dct_matrix(b):
@@ -113,13 +120,25 @@ def certify(cov, tile, b, alpha=0.1, K_A=1024.0, K_uv=1024.0, kappa=2.0, L=16, r
     return res
 
 
-def certify_rank1(cov, tile, b, alpha=0.1, iters=4):
+def certify_rank1(cov, tile, b, alpha=0.1, iters=4, scale=1.0, per_block=False, route_check=True):
     """The shipped pre-pass's bound (csrc/tmfwm_rank1.hip, round 6) restated in numpy: the top
     pair from `iters` f64 power steps on D^T D from the column-norm vector with the a-posteriori
     angle (Kato-Temple margins, Davis-Kahan) plus LAPACK's 1024 2^-53 s1 / (s1 - s2); dM in rank-one
     form (alpha' G + beta' P + gamma'); the IDCT roundings through |M_fast| <= G + |c| P; bytes at
-    both ends of [Y_fast - eps_Y, Y_fast + eps_Y].  Returns the undecided fraction and the number of
-    decided blocks whose bytes differ from the dgesdd route's (the soundness check)."""
+    both ends of [Y_fast - eps_Y, Y_fast + eps_Y].  The gate is the kernel's: a zero block, or
+    gap > 0, g1 > 0 and eps_uv <= 2^-30.  `scale` multiplies eps_Y (1.0: the bound as shipped).
+    Returns the undecided fraction and the number of decided blocks whose bytes differ from the
+    dgesdd route's (the soundness check).
+
+    per_block=True returns per-block arrays in block order (row-major over the block grid) instead:
+    `scale` may then be a sequence, and `decided[k]` for a scale k is the kernel's own rule with
+    eps_Y scaled -- the gate passes and the exact colour tail (O.ycbcr_to_rgb on the frame's own
+    chroma, the device's f32-plus-f64-redo tail equals it) gives the same three bytes at
+    f32(Y_fast - k eps_Y) and f32(Y_fast + k eps_Y) for every pixel.  Bytes are monotone in Y, so
+    decided[k] is monotone in k.  Also: `zero`, `gate`, `gate_tight` (eps_uv <= 2^-31: a block this
+    far inside the gate passes the kernel's whatever its f64 roundings), `eps_uv`, the cover's
+    blocks `blocks_rgb` (n, b, b, 3), their `tile` bytes (n,), and with route_check `differs`: the
+    blocks whose fast bytes are not the dgesdd route's."""
     H, W = cov.shape[:2]
     nbh, nbw = H // b, W // b
     ycc = O.rgb_to_ycbcr(cov)
@@ -148,8 +167,9 @@ def certify_rank1(cov, tile, b, alpha=0.1, iters=4):
     s1hi = np.sqrt(lhi) * (1 + 512 * EPS)
     s2hi = np.sqrt(np.maximum(fhi - rlo, 0)) * (1 + 512 * EPS)
     g1 = np.sqrt(rlo) * (1 - 512 * EPS) - s2hi
-    e = np.where(zero, 0.0, 1.01 * rr0 / np.where(gap > 0, gap, 1) + 1024 * EPS * s1hi / np.where(g1 > 0, g1, 1) + 2.0**-45)
-    ok = zero | ((gap > 0) & (g1 > 0))
+    e = np.where(zero, 0.0, 1.01 * rr0 / np.where(gap > 0, gap, 1) + PAIR_UNITS * EPS * s1hi / np.where(g1 > 0, g1, 1) + 2.0**-45)
+    spectral = (gap > 0) & (g1 > 0)
+    ok = zero | (spectral & (e <= GATE_EPS_UV))
     u = np.where(zero[:, None], np.eye(b)[0][None, :], t / np.sqrt(np.where(tt > 0, tt, 1))[:, None])
     v = v / np.sqrt(np.where(nv > 0, nv, 1))[:, None]
     c = alpha * (tile.reshape(-1).astype(np.float64) / 255.0)
@@ -158,7 +178,7 @@ def certify_rank1(cov, tile, b, alpha=0.1, iters=4):
     ca = np.abs(c)
     al = 1.01 * (b + 6) * U32
     be = 1.01 * ((b + 6) * U32 * ca + 2 * U32 * (s1hi + ca))
-    ga = 2.0**-40 * s1hi + ca * e * (2 + e)
+    ga = RESID_UNITS * EPS * s1hi + ca * e * (2 + e)
     # |M_ref - M_fast| <= dM = al a b^T + be u' v'^T + ga 1 1^T, and both |M_ref|, |M_fast| <= Mb =
     # (1 + al) a b^T + (|c| + be) u' v'^T + ga 1 1^T; through the f32 IDCT (tools/exp/idct_bound.py:
     # IDCT_fl(M) = C' M C'^T + R, |R| <= u (E |M| |C'|^T + |C'| |M| E^T) + u^2 E |M| E^T):
@@ -180,18 +200,41 @@ def certify_rank1(cov, tile, b, alpha=0.1, iters=4):
     Ep = _unblocks(epsY, nbh, nbw, b)
     cbp = (ycc[: nbh * b, : nbw * b, 1] - np.float32(0.5)).astype(np.float64)
     crp = (ycc[: nbh * b, : nbw * b, 2] - np.float32(0.5)).astype(np.float64)
+
+    def per_block_any(px):  # (H', W', ...) bool per pixel -> per block
+        return px.reshape(nbh, b, nbw, b, -1).any(axis=(1, 3, 4)).reshape(-1)
+
+    def fast_bytes(Y):  # the exact colour tail on the cover's own chroma with the grid's Y replaced
+        out = ycc.copy()
+        out[: nbh * b, : nbw * b, 0] = Y
+        return O.ycbcr_to_rgb(out)[: nbh * b, : nbw * b]
+
+    bd = None
+    if route_check:
+        ref = O.embed_frame(cov, tile, b, alpha, route="lapack")
+        bd = per_block_any(fast_bytes(_unblocks(Yf, nbh, nbw, b)) != ref[: nbh * b, : nbw * b])
+    if per_block:
+        decided = {}
+        for k in np.atleast_1d(scale):
+            lo, hi = (Yp - float(k) * Ep).astype(np.float32), (Yp + float(k) * Ep).astype(np.float32)
+            decided[float(k)] = ok & ~per_block_any(fast_bytes(lo) != fast_bytes(hi))
+        rgb = np.ascontiguousarray(cov[: nbh * b, : nbw * b].reshape(nbh, b, nbw, b, 3).transpose(0, 2, 1, 3, 4).reshape(n, b, b, 3))
+        res = {"zero": zero, "gate": ok, "gate_tight": zero | (spectral & (e <= GATE_EPS_UV / 2)), "eps_uv": e,
+               "decided": decided, "blocks_rgb": rgb, "tile": np.ascontiguousarray(tile, np.uint8).reshape(-1).copy()}
+        if route_check:
+            res["differs"] = bd
+        return res
+    Ep = float(scale) * Ep
     okp = np.ones(Yp.shape, bool)
     for a_cr, a_cb in ((1.403, 0.0), (-0.714, -0.344), (0.0, 1.773)):
         tcol = Yp + a_cr * crp + a_cb * cbp
         slack = Ep + 2 * U32 * np.abs(tcol) + 1e-12
         okp &= byte_of(tcol - slack) == byte_of(tcol + slack)
     cert = okp.reshape(nbh, b, nbw, b).all(axis=(1, 3)).reshape(-1) & ok
-    out_fast = ycc.copy()
-    out_fast[: nbh * b, : nbw * b, 0] = _unblocks(Yf, nbh, nbw, b)
-    fast = O.ycbcr_to_rgb(out_fast)
-    ref = O.embed_frame(cov, tile, b, alpha, route="lapack")
-    bd = (fast != ref)[: nbh * b, : nbw * b].reshape(nbh, b, nbw, b, 3).any(axis=(1, 3, 4)).reshape(-1)
-    return {"blocks": n, "undecided": float(1 - cert.mean()), "decided_blocks_differing": int((bd & cert).sum())}
+    res = {"blocks": n, "undecided": float(1 - cert.mean())}
+    if route_check:
+        res["decided_blocks_differing"] = int((bd & cert).sum())
+    return res
 
 
 def main():
