@@ -271,6 +271,53 @@ int tmfwm_embed_ragged(const tmfwm_embed_frame *frames, int64_t n_frames, int32_
 int tmfwm_extract_ragged(const tmfwm_extract_frame *frames, int64_t n_frames, int32_t block, double alpha, int32_t mem_kind,
                          void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
 
+/*
+ * Keyed extraction over ragged batches (added within ABI 10; the version number is unchanged and
+ * existing entry points keep their behaviour): the key maps and the keyed extracts of n_frames
+ * frames of mixed sizes by one set of launches, so a verifier that stores keys instead of
+ * originals takes uploads of any sizes through one call.  Frame i's key bits are exactly
+ * tmfwm_sigma1_map's on that frame alone, and its tile bytes exactly tmfwm_extract_keyed's on
+ * that frame alone with its key -- hence tmfwm_extract_route's with the original.  A key entry
+ * that is not finite gives byte 0.
+ *
+ * Descriptors, pixel layout and frames without work as the ragged block above: the descriptor
+ * array is host memory and is copied before the call returns; a frame with height < block or
+ * width < block has no block, nothing is written for it and its key, out_key and out_tile
+ * pointers are not looked at; a frame with height == 0 or width == 0 is skipped entirely.  A key
+ * is (height/block) x (width/block) float32, packed, and must be 4-byte aligned
+ * (TMFWM_ERR_INVALID otherwise, naming the frame).
+ */
+typedef struct {
+    const uint8_t *rgb;   /* height x width x 3, packed rows: the original */
+    float *out_key;       /* (height/block) x (width/block) float32, packed */
+    int32_t height, width;
+} tmfwm_key_frame;        /* 24 bytes */
+
+typedef struct {
+    const uint8_t *wm_rgb;  /* height x width x 3: the watermarked frame */
+    const float *key;       /* (height/block) x (width/block) float32: sigma1 map of its original */
+    uint8_t *out_tile;      /* (height/block) x (width/block) */
+    int32_t height, width;
+} tmfwm_keyed_frame;      /* 32 bytes */
+
+/*
+ * Memory kinds, routes, *n_lapack_blocks, the non-convergence report and the checks as
+ * tmfwm_embed_ragged: TMFWM_MEM_HOST stages every piece into one device allocation and returns
+ * when the results have landed; TMFWM_MEM_DEVICE is asynchronous on `hip_stream` unless
+ * n_lapack_blocks is given.  TMFWM_ROUTE_HYBRID certifies the enclosure in the strip pass and
+ * sends the undecided blocks straight to the dgesdd route (no list pass:
+ * tmfwm_last_list_pass_blocks() reports 0), TMFWM_ROUTE_REFERENCE sends every block there; the
+ * rank-1 routes return TMFWM_ERR_UNSUPPORTED.  With TMFWM_MEM_DEVICE every `out_key` /
+ * `out_tile` must be disjoint from every input of the call and from every other output
+ * (TMFWM_ERR_INVALID otherwise).  Inputs may share memory: many frames may point at one key (one
+ * original, many watermarked copies), the ragged form of tmfwm_extract_keyed's key_stride = 0.
+ * The map takes no alpha; the extract's must be finite and non-zero.
+ */
+int tmfwm_sigma1_map_ragged(const tmfwm_key_frame *frames, int64_t n_frames, int32_t block, int32_t mem_kind,
+                            void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
+int tmfwm_extract_keyed_ragged(const tmfwm_keyed_frame *frames, int64_t n_frames, int32_t block, double alpha,
+                               int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
+
 /* tmfwm_extract_route with a pixel layout and frame stride per input image (ABI 8). */
 int tmfwm_extract_px(const uint8_t *wm_rgb, int32_t wm_pixel_bytes, int64_t wm_frame_stride, const uint8_t *orig_rgb,
                      int32_t orig_pixel_bytes, int64_t orig_frame_stride, int64_t n_frames, int32_t height, int32_t width,

@@ -74,6 +74,19 @@ class ExtractFrame(ctypes.Structure):
                 ("height", ctypes.c_int32), ("width", ctypes.c_int32)]
 
 
+class KeyFrame(ctypes.Structure):
+    """tmfwm_key_frame: one original of tmfwm_sigma1_map_ragged (include/tmfwm.h)."""
+
+    _fields_ = [("rgb", ctypes.c_void_p), ("out_key", ctypes.c_void_p), ("height", ctypes.c_int32), ("width", ctypes.c_int32)]
+
+
+class KeyedFrame(ctypes.Structure):
+    """tmfwm_keyed_frame: one watermarked frame and its key of tmfwm_extract_keyed_ragged (include/tmfwm.h)."""
+
+    _fields_ = [("wm_rgb", ctypes.c_void_p), ("key", ctypes.c_void_p), ("out_tile", ctypes.c_void_p),
+                ("height", ctypes.c_int32), ("width", ctypes.c_int32)]
+
+
 class TileJob(ctypes.Structure):
     """tmfwm_tile_job: one job of tmfwm_prepare_tiles_ragged (include/tmfwm.h)."""
 
@@ -100,6 +113,8 @@ SIGNATURES = {
     "tmfwm_embed_tiles": (ctypes.c_int, [_VP, _I32, _I64, _I64, _I32, _I32, _VP, _I64, _I32, _D, _VP, _I32, _I64, _I32, _VP, _I32, _VP]),
     "tmfwm_embed_ragged": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _VP, _I32, _VP]),
     "tmfwm_extract_ragged": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _VP, _I32, _VP]),
+    "tmfwm_sigma1_map_ragged": (ctypes.c_int, [_VP, _I64, _I32, _I32, _VP, _I32, _VP]),
+    "tmfwm_extract_keyed_ragged": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _VP, _I32, _VP]),
     "tmfwm_extract_px": (ctypes.c_int, [_VP, _I32, _I64, _VP, _I32, _I64, _I64, _I32, _I32, _I32, _D, _VP, _I32, _VP, _I32, _VP]),
     "tmfwm_embed_multi": (ctypes.c_int, [_VP, _I64, _I32, _I32, _I64, _VP, _I32, _D, _VP, _VP, _I32, _VP]),
     "tmfwm_release_cached_buffers": (ctypes.c_int, []),

@@ -292,6 +292,99 @@ def extract_ragged(wframes, oframes, block: int = 8, alpha: float = 0.1, out=Non
     return list(out)
 
 
+def _check_ragged_out(out, shapes, dtype, dev, what: str) -> list:
+    """The caller's outputs of a ragged keyed call: one contiguous tensor of shapes[i] per frame."""
+    out = list(out)
+    if len(out) != len(shapes):
+        raise ValueError(f"out must hold one {what} per frame")
+    for i, t in enumerate(out):
+        if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shapes[i] or t.dtype != dtype or t.device != dev
+                or not t.is_contiguous()):
+            raise ValueError(f"out[{i}] must be a contiguous {shapes[i]} {dtype} tensor on {dev}")
+    return out
+
+
+def sigma1_map_ragged(frames, block: int = 8, out=None, stream=None, stats: dict | None = None, route: str = "hybrid") -> list:
+    """The extraction keys of frames of mixed sizes by one set of launches
+    (tmfwm_sigma1_map_ragged): frames[i] is (H_i, W_i, 3) uint8, contiguous, all on one GPU.
+    Returns per-frame float32 (H_i // block, W_i // block) keys, views of one device allocation
+    (or `out`, a sequence of such tensors); key i is sigma1_map(frames[i][None], ...)[0] bit for
+    bit.  stats and route ("hybrid" / "reference") as sigma1_map's; no list pass runs, so
+    "list_pass_blocks" is 0."""
+    import ctypes
+
+    if block not in SUPPORTED_BLOCK_SIZES:
+        raise NotImplementedError(f"block {block}")
+    code = _ragged_route(route)
+    frames, dev = _check_ragged(frames, "frames")
+    shapes = [(f.shape[0] // block, f.shape[1] // block) for f in frames]
+    if out is None:  # float32 views of the one uint8 allocation: its pieces start on 16-byte boundaries
+        out = [v.view(torch.float32).view(shapes[i]) for i, v in enumerate(
+            _ragged_views([4 * a * b for a, b in shapes], lambda i: (4 * shapes[i][0] * shapes[i][1],), dev))] if frames else []
+    else:
+        out = _check_ragged_out(out, shapes, torch.float32, dev, "key")
+    desc = (_lib.KeyFrame * max(len(frames), 1))()
+    for i, (f, k) in enumerate(zip(frames, out)):
+        desc[i] = _lib.KeyFrame(f.data_ptr(), k.data_ptr(), f.shape[0], f.shape[1])
+    cnt, ptr = _count_ptr(stats)
+    L = _lib.load()
+    if frames:
+        with torch.cuda.device(dev):
+            _lib.check(L.tmfwm_sigma1_map_ragged(ctypes.addressof(desc), len(frames), block, _lib.MEM_DEVICE, _stream(stream),
+                                                 code, ptr), "sigma1_map_ragged")
+    if stats is not None:
+        stats["lapack_blocks"] = int(cnt.value)
+        stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks()) if frames else 0
+    return list(out)
+
+
+def extract_keyed_ragged(wframes, keys, block: int = 8, alpha: float = 0.1, out=None, stream=None, stats: dict | None = None,
+                         route: str = "hybrid") -> list:
+    """extract_ragged without the original frames (tmfwm_extract_keyed_ragged): keys[i] is the
+    float32 (H_i // block, W_i // block) sigma1 map of wframes[i]'s original; the same tensor may
+    appear several times (one original, many watermarked copies).  Returns per-frame uint8 tiles,
+    views of one device allocation (or `out`); tile i is the bytes of
+    extract_keyed(wframes[i][None], keys[i], ...)[0], which are extract_batch's with the original.
+    A key belongs to one block size and one image size.  stats and route as sigma1_map_ragged's."""
+    import ctypes
+
+    if block not in SUPPORTED_BLOCK_SIZES:
+        raise NotImplementedError(f"block {block}")
+    code = _ragged_route(route)
+    wframes, keys = list(wframes), list(keys)
+    if len(keys) != len(wframes):
+        raise ValueError(f"{len(keys)} keys for {len(wframes)} frames")
+    # what a key is, and whether it fits its frame, before any tensor's device is looked at
+    for i, (w, k) in enumerate(zip(wframes, keys)):
+        if not isinstance(k, torch.Tensor) or k.dtype != torch.float32:
+            raise TypeError(f"keys[{i}] must be a float32 tensor")
+        if isinstance(w, torch.Tensor) and w.dim() == 3 and tuple(k.shape) != (w.shape[0] // block, w.shape[1] // block):
+            raise ValueError(f"keys[{i}] must be {(w.shape[0] // block, w.shape[1] // block)} for block {block} and a "
+                             f"{w.shape[1]}x{w.shape[0]} frame, got {tuple(k.shape)}: a key belongs to one block size and one image size")
+    wframes, dev = _check_ragged(wframes, "wframes")
+    shapes = [(w.shape[0] // block, w.shape[1] // block) for w in wframes]
+    for i, k in enumerate(keys):
+        if k.device != dev or not k.is_contiguous():
+            raise ValueError(f"keys[{i}] must be contiguous and on {dev}")
+    if out is None:
+        out = _ragged_views([a * b for a, b in shapes], lambda i: shapes[i], dev) if wframes else []
+    else:
+        out = _check_ragged_out(out, shapes, torch.uint8, dev, "tile")
+    desc = (_lib.KeyedFrame * max(len(wframes), 1))()
+    for i, (w, k, t) in enumerate(zip(wframes, keys, out)):
+        desc[i] = _lib.KeyedFrame(w.data_ptr(), k.data_ptr(), t.data_ptr(), w.shape[0], w.shape[1])
+    cnt, ptr = _count_ptr(stats)
+    L = _lib.load()
+    if wframes:
+        with torch.cuda.device(dev):
+            _lib.check(L.tmfwm_extract_keyed_ragged(ctypes.addressof(desc), len(wframes), block, float(alpha), _lib.MEM_DEVICE,
+                                                    _stream(stream), code, ptr), "extract_keyed_ragged")
+    if stats is not None:
+        stats["lapack_blocks"] = int(cnt.value)
+        stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks()) if wframes else 0
+    return list(out)
+
+
 def synth_frames(n: int, height: int, width: int, seed: int = SEED_COVER, frame0: int = 0,
                  device: torch.device | str | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
     """Counter-based synthetic uint8 frames generated directly in HBM."""

@@ -1365,39 +1365,67 @@ int tmfwm_prepare_tile(const uint8_t *wm, int32_t wm_height, int32_t wm_width, i
 extern "C++" {
 namespace {
 
-// One frame of a ragged call once its descriptor is checked (embed: in0 = rgb, in1 = wm_tile;
-// extract: in0 = wm_rgb, in1 = orig_rgb); the descriptor array is not read after that.
+// What a ragged call does with its frames.  The kind decides each piece's byte count, which
+// pieces are inputs, whether an edge pass runs and which launchers run.
+enum class RKind {
+    Embed,    // in0 = rgb, in1 = wm_tile (bytes), out = the output pixels
+    Extract,  // in0 = wm_rgb, in1 = orig_rgb, out = out_tile (bytes)
+    Map,      // in0 = rgb, no in1, out = out_key (floats)
+    Keyed,    // in0 = wm_rgb, in1 = key (floats), out = out_tile (bytes)
+};
+
+// One frame of a ragged call once its descriptor is checked; the descriptor array is not read
+// after that.
 struct RFrame {
     const uint8_t *in0, *in1;
     uint8_t *out;
     int32_t H, W;
     int64_t pixel_bytes() const { return (int64_t)H * W * 3; }
     int64_t tile_bytes(int b) const { return (int64_t)(H / b) * (W / b); }
+    // the bytes behind in1 and out
+    int64_t in1_bytes(RKind k, int b) const
+    {
+        return k == RKind::Embed ? tile_bytes(b) : k == RKind::Extract ? pixel_bytes() : k == RKind::Keyed ? tile_bytes(b) * 4 : 0;
+    }
+    int64_t out_bytes(RKind k, int b) const
+    {
+        return k == RKind::Embed ? pixel_bytes() : k == RKind::Map ? tile_bytes(b) * 4 : tile_bytes(b);
+    }
+    // embed writes every frame that has a pixel (its colour round trip); the others only frames with a block
+    bool has_work(RKind k, int b) const { return pixel_bytes() > 0 && (k == RKind::Embed || tile_bytes(b) > 0); }
 };
 
+const char *const kRaggedNames[4][3] = {{"rgb", "wm_tile", "out"}, {"wm_rgb", "orig_rgb", "out_tile"}, {"rgb", "", "out_key"},
+                                        {"wm_rgb", "key", "out_tile"}};
+
 // the checks every ragged call makes before it touches the device
-int check_ragged_call(const void *frames, int64_t n, int32_t block, double alpha, bool extract, int32_t mem_kind, int32_t route,
+int check_ragged_call(const void *frames, int64_t n, int32_t block, double alpha, RKind kind, int32_t mem_kind, int32_t route,
                       int64_t *n_lapack)
 {
+    const bool extract = kind == RKind::Extract || kind == RKind::Keyed;
     if (int rc = begin_call(route, n_lapack, false)) return rc;  // no rank-1 routes yet; no list pass in a ragged call
     if (n < 0) return fail(TMFWM_ERR_INVALID, "negative size (n=%lld)", (long long)n);
     if (n > 0 && !frames) return fail(TMFWM_ERR_INVALID, "frames is NULL");
     if (!supported_block(block)) return fail(TMFWM_ERR_UNSUPPORTED, "block size %d not supported (even, 4..16)", block);
     if (mem_kind != TMFWM_MEM_HOST && mem_kind != TMFWM_MEM_DEVICE) return fail(TMFWM_ERR_INVALID, "mem_kind %d", mem_kind);
-    if (extract ? (!std::isfinite(alpha) || alpha == 0.0) : !std::isfinite(alpha))
+    if (kind != RKind::Map && (extract ? (!std::isfinite(alpha) || alpha == 0.0) : !std::isfinite(alpha)))  // the map takes no alpha
         return fail(TMFWM_ERR_INVALID, extract ? "alpha must be finite and non-zero" : "alpha is not finite");
     return 0;
 }
 
-// one frame's sizes and pointers (the tile pointer only where the frame has a block)
-int check_ragged_frame(int64_t i, const RFrame &f, int32_t block, bool extract)
+// one frame's sizes and pointers (the tile and key pointers only where the frame has a block)
+int check_ragged_frame(int64_t i, const RFrame &f, int32_t block, RKind kind)
 {
     if (int rc = check_frames(1, f.H, f.W, f.pixel_bytes(), block)) return fail(rc, "frame %lld: %s", (long long)i, t_err.c_str());
     if (f.H == 0 || f.W == 0) return 0;
     if (f.tile_bytes(block) > 0x7FFFFFFFll) return fail(TMFWM_ERR_INVALID, "frame %lld: more than 2^31 - 1 blocks", (long long)i);
     const bool tile = f.tile_bytes(block) > 0;
-    if (extract ? (tile && (!f.in0 || !f.in1 || !f.out)) : (!f.in0 || !f.out || (tile && !f.in1)))
+    if (kind == RKind::Embed ? (!f.in0 || !f.out || (tile && !f.in1)) : (tile && (!f.in0 || (kind != RKind::Map && !f.in1) || !f.out)))
         return fail(TMFWM_ERR_INVALID, "frame %lld: NULL pointer in the descriptor", (long long)i);
+    // the float pieces are read and written as floats
+    const uint8_t *fl = kind == RKind::Keyed ? f.in1 : kind == RKind::Map ? f.out : nullptr;
+    if (tile && reinterpret_cast<uintptr_t>(fl) % 4)
+        return fail(TMFWM_ERR_INVALID, "frame %lld: %s is not 4-byte aligned", (long long)i, kRaggedNames[(int)kind][kind == RKind::Keyed ? 1 : 2]);
     return 0;
 }
 
@@ -1425,8 +1453,9 @@ int check_ragged_overlap(std::vector<Span> &spans, const char *unit = "frame")  
     return 0;
 }
 
-int check_ragged_device(const std::vector<RFrame> &fr, int32_t block, bool extract)
+int check_ragged_device(const std::vector<RFrame> &fr, int32_t block, RKind kind)
 {
+    const char *const *name = kRaggedNames[(int)kind];
     std::vector<Span> spans;
     spans.reserve(fr.size() * 3);
     auto add = [&](const void *p, int64_t bytes, bool out, int64_t i) {
@@ -1435,15 +1464,15 @@ int check_ragged_device(const std::vector<RFrame> &fr, int32_t block, bool extra
     };
     for (size_t i = 0; i < fr.size(); ++i) {
         const RFrame &f = fr[i];
-        const int64_t px = f.pixel_bytes(), tb = f.tile_bytes(block);
-        if (px == 0 || (extract && tb == 0)) continue;
-        if (int rc = check_device_ptr(f.in0, extract ? "wm_rgb" : "rgb")) return rc;
-        if (extract || tb)
-            if (int rc = check_device_ptr(f.in1, extract ? "orig_rgb" : "wm_tile")) return rc;
-        if (int rc = check_device_ptr(f.out, extract ? "out_tile" : "out")) return rc;
-        add(f.in0, px, false, (int64_t)i);
-        add(f.in1, extract ? px : tb, false, (int64_t)i);
-        add(f.out, extract ? tb : px, true, (int64_t)i);
+        const int64_t ib = f.in1_bytes(kind, block);
+        if (!f.has_work(kind, block)) continue;
+        if (int rc = check_device_ptr(f.in0, name[0])) return rc;
+        if (ib)
+            if (int rc = check_device_ptr(f.in1, name[1])) return rc;
+        if (int rc = check_device_ptr(f.out, name[2])) return rc;
+        add(f.in0, f.pixel_bytes(), false, (int64_t)i);
+        if (ib) add(f.in1, ib, false, (int64_t)i);
+        add(f.out, f.out_bytes(kind, block), true, (int64_t)i);
     }
     return check_ragged_overlap(spans);
 }
@@ -1519,7 +1548,7 @@ struct RaggedChunk {
 constexpr int64_t kEdgeCap = int64_t(1) << 38;
 
 // the frame table of the frames that have work, with chunk-relative prefixes, and the chunks
-void plan_ragged(const std::vector<RFrame> &fr, int32_t block, bool extract, std::vector<tmf::RaggedFrame> &table,
+void plan_ragged(const std::vector<RFrame> &fr, int32_t block, RKind kind, std::vector<tmf::RaggedFrame> &table,
                  std::vector<RaggedChunk> &chunks)
 {
     const int bpw = tmf::ragged_strip_blocks(block);
@@ -1535,9 +1564,10 @@ void plan_ragged(const std::vector<RFrame> &fr, int32_t block, bool extract, std
         t.nbh = f.H / block;
         t.nbw = f.W / block;
         t.strips_per_row = (t.nbw + bpw - 1) / bpw;
-        t.aligned = tmf::dev_aligned(f.in0, extract ? f.in1 : f.out, 0, f.W);
+        // the frame's pixel buffers: two of them, or the single one of the keyed calls
+        t.aligned = tmf::dev_aligned(f.in0, kind == RKind::Embed ? f.out : kind == RKind::Extract ? f.in1 : f.in0, 0, f.W);
         const int64_t waves = (int64_t)t.nbh * t.strips_per_row, blocks = (int64_t)t.nbh * t.nbw;
-        const int64_t edge = extract ? 0 : (int64_t)f.H * f.W - blocks * block * block;
+        const int64_t edge = kind == RKind::Embed ? (int64_t)f.H * f.W - blocks * block * block : 0;
         if (blocks == 0 && edge == 0) continue;
         if (c.n > 0 && (c.blocks + blocks > cap || c.edge + edge > kEdgeCap)) {
             chunks.push_back(c);
@@ -1559,7 +1589,7 @@ void plan_ragged(const std::vector<RFrame> &fr, int32_t block, bool extract, std
 // Both passes of a ragged call over device-resident frames: the frame table uploaded, then the
 // chunks through two_pass, with the edge pass between a chunk's first pass and its fixup pass and
 // neither of the two for a chunk without a block.
-int run_ragged(int32_t block, double alpha, bool extract, hipStream_t st, int route, const Report &rep,
+int run_ragged(int32_t block, double alpha, RKind kind, hipStream_t st, int route, const Report &rep,
                const std::vector<tmf::RaggedFrame> &table, const std::vector<RaggedChunk> &chunks)
 {
     if (chunks.empty()) return 0;
@@ -1588,32 +1618,38 @@ int run_ragged(int32_t block, double alpha, bool extract, hipStream_t st, int ro
         r.fb_bad = w.fb_bad;
         if (k.blocks > 0) {
             if (route == TMFWM_ROUTE_REFERENCE) TMF_HIP(tmf::launch_list_all(r.fb_list, r.fb_count, k.blocks, st));
-            else TMF_HIP(extract ? tmf::launch_extract_ragged(r, k.waves, st) : tmf::launch_embed_ragged(r, k.waves, st));
+            else
+                TMF_HIP(kind == RKind::Embed     ? tmf::launch_embed_ragged(r, k.waves, st)
+                        : kind == RKind::Extract ? tmf::launch_extract_ragged(r, k.waves, st)
+                        : kind == RKind::Map     ? tmf::launch_sigma1_map_ragged(r, k.waves, st)
+                                                 : tmf::launch_extract_keyed_ragged(r, k.waves, st));
         }
-        if (!extract) TMF_HIP(tmf::launch_edges_ragged(r, k.edge, st));
+        if (kind == RKind::Embed) TMF_HIP(tmf::launch_edges_ragged(r, k.edge, st));
         if (k.blocks > 0)
-            TMF_HIP(extract ? tmf::launch_extract_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st)
-                            : tmf::launch_embed_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st));
+            TMF_HIP(kind == RKind::Embed     ? tmf::launch_embed_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st)
+                    : kind == RKind::Extract ? tmf::launch_extract_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st)
+                    : kind == RKind::Map     ? tmf::launch_sigma1_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st)
+                                             : tmf::launch_extract_keyed_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st));
         return 0;
     });
 }
 
 size_t round16(size_t n) { return (n + 15) & ~size_t(15); }
 
-int ragged_call(std::vector<RFrame> &fr, int32_t block, double alpha, bool extract, int32_t mem_kind, void *hip_stream, int32_t route,
+int ragged_call(std::vector<RFrame> &fr, int32_t block, double alpha, RKind kind, int32_t mem_kind, void *hip_stream, int32_t route,
                 int64_t *n_lapack)
 {
     for (size_t i = 0; i < fr.size(); ++i)
-        if (int rc = check_ragged_frame((int64_t)i, fr[i], block, extract)) return rc;
+        if (int rc = check_ragged_frame((int64_t)i, fr[i], block, kind)) return rc;
     if (int rc = need_device()) return rc;
     if (fr.empty()) return 0;
     hipStream_t st = pick_stream(hip_stream);
     std::vector<tmf::RaggedFrame> table;
     std::vector<RaggedChunk> chunks;
     if (mem_kind == TMFWM_MEM_DEVICE) {
-        if (int rc = check_ragged_device(fr, block, extract)) return rc;
-        plan_ragged(fr, block, extract, table, chunks);
-        return run_ragged(block, alpha, extract, st, route, device_report(n_lapack), table, chunks);
+        if (int rc = check_ragged_device(fr, block, kind)) return rc;
+        plan_ragged(fr, block, kind, table, chunks);
+        return run_ragged(block, alpha, kind, st, route, device_report(n_lapack), table, chunks);
     }
     // host memory: every buffer of the call in one device allocation (16-byte aligned pieces),
     // results copied back, one synchronisation
@@ -1621,8 +1657,7 @@ int ragged_call(std::vector<RFrame> &fr, int32_t block, double alpha, bool extra
     size_t total = 0;
     std::vector<size_t> off(fr.size() * 3);
     for (size_t i = 0; i < fr.size(); ++i) {
-        const size_t px = (size_t)fr[i].pixel_bytes(), tb = (size_t)fr[i].tile_bytes(block);
-        const size_t sz[3] = {px, extract ? px : tb, extract ? tb : px};
+        const size_t sz[3] = {(size_t)fr[i].pixel_bytes(), (size_t)fr[i].in1_bytes(kind, block), (size_t)fr[i].out_bytes(kind, block)};
         for (int k = 0; k < 3; ++k) {
             off[3 * i + k] = total;
             total += round16(sz[k]);
@@ -1632,22 +1667,20 @@ int ragged_call(std::vector<RFrame> &fr, int32_t block, double alpha, bool extra
     if (int rc = stage.alloc(total, st, "ragged frames")) return rc;
     uint8_t *base = static_cast<uint8_t *>(stage.p);
     for (size_t i = 0; i < fr.size(); ++i) {
-        const size_t px = (size_t)fr[i].pixel_bytes(), tb = (size_t)fr[i].tile_bytes(block);
-        if (px == 0 || (extract && tb == 0)) continue;
+        const size_t ib = (size_t)fr[i].in1_bytes(kind, block);
+        if (!fr[i].has_work(kind, block)) continue;
         dv[i].in0 = base + off[3 * i];
-        dv[i].in1 = base + off[3 * i + 1];
+        dv[i].in1 = ib ? base + off[3 * i + 1] : nullptr;
         dv[i].out = base + off[3 * i + 2];
-        TMF_HIP(hipMemcpyAsync(base + off[3 * i], fr[i].in0, px, hipMemcpyHostToDevice, st));
-        if (extract || tb) TMF_HIP(hipMemcpyAsync(base + off[3 * i + 1], fr[i].in1, extract ? px : tb, hipMemcpyHostToDevice, st));
+        TMF_HIP(hipMemcpyAsync(base + off[3 * i], fr[i].in0, (size_t)fr[i].pixel_bytes(), hipMemcpyHostToDevice, st));
+        if (ib) TMF_HIP(hipMemcpyAsync(base + off[3 * i + 1], fr[i].in1, ib, hipMemcpyHostToDevice, st));
     }
-    plan_ragged(dv, block, extract, table, chunks);
+    plan_ragged(dv, block, kind, table, chunks);
     HostCall hc((int64_t)chunks.size(), st, n_lapack);
-    if (int rc = run_ragged(block, alpha, extract, st, route, hc.report(), table, chunks)) return rc;
+    if (int rc = run_ragged(block, alpha, kind, st, route, hc.report(), table, chunks)) return rc;
     for (size_t i = 0; i < fr.size(); ++i) {
-        const size_t px = (size_t)fr[i].pixel_bytes(), tb = (size_t)fr[i].tile_bytes(block);
-        const size_t ob = extract ? tb : px;
-        if (px == 0 || ob == 0) continue;
-        TMF_HIP(hipMemcpyAsync(fr[i].out, dv[i].out, ob, hipMemcpyDeviceToHost, st));
+        if (!fr[i].has_work(kind, block)) continue;
+        TMF_HIP(hipMemcpyAsync(fr[i].out, dv[i].out, (size_t)fr[i].out_bytes(kind, block), hipMemcpyDeviceToHost, st));
     }
     return hc.finish();
 }
@@ -1761,20 +1794,42 @@ int tiles_ragged_call(std::vector<tmf::TileJobIn> &jobs, bool preserve_ratio, in
 int tmfwm_embed_ragged(const tmfwm_embed_frame *frames, int64_t n_frames, int32_t block, double alpha, int32_t mem_kind,
                        void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
 {
-    if (int rc = check_ragged_call(frames, n_frames, block, alpha, false, mem_kind, route, n_lapack_blocks)) return rc;
+    if (int rc = check_ragged_call(frames, n_frames, block, alpha, RKind::Embed, mem_kind, route, n_lapack_blocks)) return rc;
     std::vector<RFrame> fr((size_t)n_frames);  // the library's copy: the caller's array is not read again
     for (int64_t i = 0; i < n_frames; ++i) fr[(size_t)i] = {frames[i].rgb, frames[i].wm_tile, frames[i].out, frames[i].height, frames[i].width};
-    return ragged_call(fr, block, alpha, false, mem_kind, hip_stream, route, n_lapack_blocks);
+    return ragged_call(fr, block, alpha, RKind::Embed, mem_kind, hip_stream, route, n_lapack_blocks);
 }
 
 int tmfwm_extract_ragged(const tmfwm_extract_frame *frames, int64_t n_frames, int32_t block, double alpha, int32_t mem_kind,
                          void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
 {
-    if (int rc = check_ragged_call(frames, n_frames, block, alpha, true, mem_kind, route, n_lapack_blocks)) return rc;
+    if (int rc = check_ragged_call(frames, n_frames, block, alpha, RKind::Extract, mem_kind, route, n_lapack_blocks)) return rc;
     std::vector<RFrame> fr((size_t)n_frames);
     for (int64_t i = 0; i < n_frames; ++i)
         fr[(size_t)i] = {frames[i].wm_rgb, frames[i].orig_rgb, frames[i].out_tile, frames[i].height, frames[i].width};
-    return ragged_call(fr, block, alpha, true, mem_kind, hip_stream, route, n_lapack_blocks);
+    return ragged_call(fr, block, alpha, RKind::Extract, mem_kind, hip_stream, route, n_lapack_blocks);
+}
+
+// keyed extraction over ragged batches: the key rides in the frame's in1 / out slot as bytes
+int tmfwm_sigma1_map_ragged(const tmfwm_key_frame *frames, int64_t n_frames, int32_t block, int32_t mem_kind, void *hip_stream,
+                            int32_t route, int64_t *n_lapack_blocks)
+{
+    if (int rc = check_ragged_call(frames, n_frames, block, 1.0, RKind::Map, mem_kind, route, n_lapack_blocks)) return rc;
+    std::vector<RFrame> fr((size_t)n_frames);
+    for (int64_t i = 0; i < n_frames; ++i)
+        fr[(size_t)i] = {frames[i].rgb, nullptr, reinterpret_cast<uint8_t *>(frames[i].out_key), frames[i].height, frames[i].width};
+    return ragged_call(fr, block, 1.0, RKind::Map, mem_kind, hip_stream, route, n_lapack_blocks);
+}
+
+int tmfwm_extract_keyed_ragged(const tmfwm_keyed_frame *frames, int64_t n_frames, int32_t block, double alpha, int32_t mem_kind,
+                               void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    if (int rc = check_ragged_call(frames, n_frames, block, alpha, RKind::Keyed, mem_kind, route, n_lapack_blocks)) return rc;
+    std::vector<RFrame> fr((size_t)n_frames);
+    for (int64_t i = 0; i < n_frames; ++i)
+        fr[(size_t)i] = {frames[i].wm_rgb, reinterpret_cast<const uint8_t *>(frames[i].key), frames[i].out_tile, frames[i].height,
+                         frames[i].width};
+    return ragged_call(fr, block, alpha, RKind::Keyed, mem_kind, hip_stream, route, n_lapack_blocks);
 }
 
 int tmfwm_prepare_tiles_ragged(const tmfwm_tile_job *jobs, int64_t n_jobs, int32_t preserve_ratio, int32_t mem_kind,

@@ -11,26 +11,7 @@
 
 namespace tmf {
 
-// waves per SIMD the register allocation must allow: one image's rows and one power iteration
-// live at a time, so the pair kernels' bounds hold with room to spare
-template <int B>
-constexpr int kKeyedWaves = B > 8 ? 2 : kExtract8Waves;
-
-// sigma_1 of this wave's blocks of the one image (pos per lane), certified or not (ok)
-template <int B, int ITERS>
-TMF_DEVI void keyed_sigma(const KeyedArgs &a, const StripPos &pos, float *tile, int q, float &s, bool &ok)
-{
-    constexpr int R = Geo<B>::R, L = Geo<B>::L;
-    uint32_t w[R][Geo<B>::NW];
-    float x[1][R][B], s1[1];
-    bool k[1];
-    load_block_rows<B>(a.src + pos.frame * a.frame_stride, a.W, pos, q, a.aligned, w);
-    dct_rows_of<B>(w, q, tile, x[0]);
-    sigma1_certified<B, L, ITERS, 1>(x, s1, k);
-    s = s1[0];
-    ok = k[0];
-}
-
+// (kKeyedWaves and keyed_sigma, the strip body of one image: tmfwm_keyed.h)
 template <int B, bool LIST, bool MAP>
 TMF_DEVI void keyed_pass(const KeyedArgs &a)
 {

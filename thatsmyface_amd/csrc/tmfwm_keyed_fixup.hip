@@ -12,21 +12,6 @@
 
 namespace tmf {
 
-template <int B, class Par, int G, bool MAP>
-TMF_DEVI void keyed_fix_block(const KeyedArgs &a, uint32_t id, FixLdsS<B> &f, int gl)
-{
-    const uint32_t per_frame = (uint32_t)a.nbh * (uint32_t)a.nbw;
-    int64_t fr;
-    int bi, bj;
-    block_of(id, per_frame, a.nbw, fr, bi, bj);
-    fix_load_dct<B, G>(a.src + fr * a.frame_stride, a.W, bi, bj, f.D, gl);
-    const int info = lp::svd_f32_ws<false, Par>(f.D, runtime_n(B), nullptr, f.S, nullptr, f.ws);  // :279-282
-    if (info && gl == 0 && a.fb_bad) atomicAdd(a.fb_bad, 1u);
-    const float s = f.S[0];
-    group_sync();  // the LDS slots are reused by the next listed block
-    if (gl == 0) keyed_store<MAP>(a, fr, bi, bj, s);
-}
-
 template <int B, bool MAP>
 TMF_DEVI void keyed_fixup(const KeyedArgs &a, const uint32_t *__restrict__ list, const uint32_t *__restrict__ count)
 {

@@ -1,10 +1,11 @@
-// Ragged batches (tmfwm_embed_ragged / tmfwm_extract_ragged): frames of mixed sizes, each with
-// its own buffers, through one set of launches.
+// Ragged batches (tmfwm_embed_ragged / tmfwm_extract_ragged, and keyed extraction's
+// tmfwm_sigma1_map_ragged / tmfwm_extract_keyed_ragged): frames of mixed sizes, each with its own
+// buffers, through one set of launches.
 //
 // The host builds a frame table -- one RaggedFrame per frame, with the exclusive prefix sums of
 // the frames' strip waves, blocks and edge pixels -- and uploads it in one copy.  A ragged
-// kernel finds its frame by binary search in a prefix, builds the EmbedArgs / ExtractArgs of
-// that one frame (nframes = 1, strides 0, no list pass) and calls the device function of the
+// kernel finds its frame by binary search in a prefix, builds the EmbedArgs / ExtractArgs /
+// KeyedArgs of that one frame (nframes = 1, strides 0, no list pass) and calls the device function of the
 // single-size kernel with it, so a frame's bytes are the single-size path's by construction.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,11 +16,13 @@
 namespace tmf {
 
 struct RaggedFrame {
-    const uint8_t *in0;  // embed: the frame's pixels; extract: the watermarked frame
-    const uint8_t *in1;  // embed: its nbh x nbw tile; extract: the original frame
-    uint8_t *out;        // embed: the output pixels; extract: the nbh x nbw tile
+    const uint8_t *in0;  // embed: the frame's pixels; extract, keyed extract: the watermarked frame; map: the original
+    const uint8_t *in1;  // embed: its nbh x nbw tile; extract: the original frame; keyed extract: its nbh x nbw f32 key
+                         // (4-byte aligned, read as const float *); map: null
+    uint8_t *out;        // embed: the output pixels; extract, keyed extract: the nbh x nbw tile; map: the nbh x nbw
+                         // f32 key output (4-byte aligned, written as float *)
     int32_t H, W, nbh, nbw, strips_per_row;
-    int32_t aligned;     // as dev_aligned: both pixel buffers 4-byte aligned and W % 4 == 0
+    int32_t aligned;     // as dev_aligned: the pixel buffers (both, or the one of the keyed calls) 4-byte aligned and W % 4 == 0
     // exclusive prefix sums over the frames of the chunk (the launches' flat indices):
     uint32_t wave0;      // strip waves, nbh * strips_per_row per frame
     uint32_t block0;     // blocks, nbh * nbw per frame: the block-list ids are block0 + bi * nbw + bj
@@ -42,6 +45,8 @@ int ragged_strip_blocks(int block);
 // strip pass of a chunk: `waves` = the chunk's strip waves (> 0), one workgroup each
 hipError_t launch_embed_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st);
 hipError_t launch_extract_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st);
+hipError_t launch_sigma1_map_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st);
+hipError_t launch_extract_keyed_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st);
 // colour round trip of the chunk's `pixels` edge pixels (embed)
 hipError_t launch_edges_ragged(const RaggedArgs &r, int64_t pixels, hipStream_t st);
 // the dgesdd route over the chunk's list (ids as above), max_entries bounds the list
@@ -49,7 +54,11 @@ hipError_t launch_embed_ragged_fixup(const RaggedArgs &r, const uint32_t *list, 
                                      hipStream_t st);
 hipError_t launch_extract_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
                                        hipStream_t st);
-// the four launchers per block size B: defined and instantiated for B = TMF_B in the size's own
+hipError_t launch_sigma1_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
+                                      hipStream_t st);
+hipError_t launch_extract_keyed_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
+                                             hipStream_t st);
+// the eight launchers per block size B: defined and instantiated for B = TMF_B in the size's own
 // translation units (tmfwm_ragged_strip.hip, tmfwm_ragged_fixup.hip), which alone see the kernels
 template <int B>
 hipError_t embed_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st);
@@ -59,6 +68,15 @@ template <int B>
 hipError_t embed_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
 template <int B>
 hipError_t extract_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
+template <int B>
+hipError_t sigma1_map_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st);
+template <int B>
+hipError_t extract_keyed_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st);
+template <int B>
+hipError_t sigma1_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
+template <int B>
+hipError_t extract_keyed_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
+                                        hipStream_t st);
 
 #if defined(__HIPCC__)
 // The table through the constant address space: a load from it at a wave-uniform address is a
@@ -120,6 +138,36 @@ __device__ __forceinline__ ExtractArgs ragged_extract_view(const RaggedArgs &r, 
     a.nframes = 1;
     a.frame_stride = 0;
     a.tile_stride = 0;
+    a.H = f->H;
+    a.W = f->W;
+    a.block = r.block;
+    a.nbh = f->nbh;
+    a.nbw = f->nbw;
+    a.strips_per_row = f->strips_per_row;
+    a.aligned = f->aligned;
+    a.alpha32 = r.alpha32;
+    a.fb_list = r.fb_list;
+    a.fb_count = r.fb_count;
+    a.fb_bad = r.fb_bad;
+    a.slow_list = nullptr;  // undecided blocks go straight to the dgesdd route
+    a.slow_count = nullptr;
+    a.slow_shards = nullptr;
+    return a;
+}
+
+// keyed extraction: one image per frame; in1 is the key (keyed extract), out the key output (map) or the tile
+template <class F>
+__device__ __forceinline__ KeyedArgs ragged_keyed_view(const RaggedArgs &r, F *f)
+{
+    KeyedArgs a;
+    a.src = f->in0;
+    a.key = (const float *)f->in1;
+    a.key_out = (float *)f->out;
+    a.out = f->out;
+    a.nframes = 1;
+    a.frame_stride = 0;
+    a.tile_stride = 0;
+    a.key_stride = 0;
     a.H = f->H;
     a.W = f->W;
     a.block = r.block;

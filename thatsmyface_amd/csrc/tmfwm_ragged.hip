@@ -25,6 +25,18 @@ hipError_t launch_extract_ragged(const RaggedArgs &r, int64_t waves, hipStream_t
     return for_block(r.block, [&](auto b) { return extract_ragged_b<b()>(r, (unsigned)waves, st); });
 }
 
+hipError_t launch_sigma1_map_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st)
+{
+    if (waves <= 0 || waves > kGridMax) return hipErrorInvalidValue;
+    return for_block(r.block, [&](auto b) { return sigma1_map_ragged_b<b()>(r, (unsigned)waves, st); });
+}
+
+hipError_t launch_extract_keyed_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st)
+{
+    if (waves <= 0 || waves > kGridMax) return hipErrorInvalidValue;
+    return for_block(r.block, [&](auto b) { return extract_keyed_ragged_b<b()>(r, (unsigned)waves, st); });
+}
+
 hipError_t launch_embed_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
                                      hipStream_t st)
 {
@@ -35,6 +47,18 @@ hipError_t launch_extract_ragged_fixup(const RaggedArgs &r, const uint32_t *list
                                        hipStream_t st)
 {
     return for_block(r.block, [&](auto b) { return extract_ragged_fixup_b<b()>(r, list, count, max_entries, st); });
+}
+
+hipError_t launch_sigma1_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
+                                      hipStream_t st)
+{
+    return for_block(r.block, [&](auto b) { return sigma1_ragged_fixup_b<b()>(r, list, count, max_entries, st); });
+}
+
+hipError_t launch_extract_keyed_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
+                                             hipStream_t st)
+{
+    return for_block(r.block, [&](auto b) { return extract_keyed_ragged_fixup_b<b()>(r, list, count, max_entries, st); });
 }
 
 // The edge pixels of every frame of the chunk on one flat index over the table's edge prefix;

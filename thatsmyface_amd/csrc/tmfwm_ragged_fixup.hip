@@ -1,9 +1,10 @@
 // dgesdd-route second passes of the ragged calls (tmfwm_ragged.h) for one block size,
 // TMF_B: compiled once per size (tmfwm_ragged_fixup<b>.o), as their single-size siblings are
 // (tmfwm_fixup.hip).  The walk over the list is theirs (fixup_walk); each listed id's frame is found
-// in the table's block prefix and embed_fix_block / extract_fix_block run on that frame's
-// one-frame view.
+// in the table's block prefix and embed_fix_block / extract_fix_block / keyed_fix_block run on
+// that frame's one-frame view.
 #include "tmfwm_fixup.h"
+#include "tmfwm_keyed.h"
 #include "tmfwm_ragged.h"
 
 #ifndef TMF_B
@@ -52,6 +53,49 @@ __global__ __launch_bounds__(64) void extract_ragged_fixup_kernel(RaggedArgs r, 
     });
 }
 
+// keyed extraction (tmfwm_keyed.h): keyed_fix_block on the frame's one image
+template <int B, bool MAP>
+TMF_DEVI void keyed_ragged_fixup(const RaggedArgs &r, const uint32_t *__restrict__ list, const uint32_t *__restrict__ count)
+{
+    fixup_walk<B, FixLdsS<B>>(list, count, [&](auto par, uint32_t id, FixLdsS<B> &f, int gl) {
+        const RaggedFrame *fr = ragged_block_frame(r, id);
+        const KeyedArgs a = ragged_keyed_view(r, fr);
+        keyed_fix_block<B, typename decltype(par)::Par, decltype(par)::G, MAP>(a, id - fr->block0, f, gl);
+    });
+}
+
+template <int B>
+__global__ __launch_bounds__(64) void sigma1_ragged_fixup_kernel(RaggedArgs r, const uint32_t *__restrict__ list,
+                                                                 const uint32_t *__restrict__ count)
+{
+    keyed_ragged_fixup<B, true>(r, list, count);
+}
+
+// the waves per SIMD of extract_keyed_fixup_kernel<B>: the frame's key and tile pointers are per
+// lane here, which at b = 4 costs the two VGPRs that would otherwise drop it to 3
+template <int B>
+constexpr int kKeyedFixWaves = B <= 12 ? 4 : 3;
+
+template <int B>
+__global__ __launch_bounds__(64, kKeyedFixWaves<B>) void extract_keyed_ragged_fixup_kernel(RaggedArgs r, const uint32_t *__restrict__ list,
+                                                                        const uint32_t *__restrict__ count)
+{
+    keyed_ragged_fixup<B, false>(r, list, count);
+}
+
+template <int B>
+hipError_t sigma1_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st)
+{
+    return launch_fixup<B>(sigma1_ragged_fixup_kernel<B>, r, list, count, max_entries, st);
+}
+
+template <int B>
+hipError_t extract_keyed_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
+                                        hipStream_t st)
+{
+    return launch_fixup<B>(extract_keyed_ragged_fixup_kernel<B>, r, list, count, max_entries, st);
+}
+
 template <int B>
 hipError_t embed_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st)
 {
@@ -66,5 +110,7 @@ hipError_t extract_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, con
 
 template hipError_t embed_ragged_fixup_b<TMF_B>(const RaggedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
 template hipError_t extract_ragged_fixup_b<TMF_B>(const RaggedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
+template hipError_t sigma1_ragged_fixup_b<TMF_B>(const RaggedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
+template hipError_t extract_keyed_ragged_fixup_b<TMF_B>(const RaggedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
 
 }  // namespace tmf

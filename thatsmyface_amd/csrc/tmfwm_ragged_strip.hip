@@ -1,16 +1,24 @@
 // Strip passes of the ragged calls (tmfwm_ragged.h) for one block size, TMF_B: the
 // Makefile compiles this file once per size (tmfwm_ragged_strip<b>.o), b = 8 under the same
-// max-ILP scheduler as its single-size sibling embed_kernel<8> (tmfwm_embed8.hip).
+// max-ILP scheduler as its single-size sibling embed_kernel<8> (tmfwm_embed8.hip).  The keyed
+// kernels' single-size siblings (tmfwm_keyed.hip) are compiled under the default scheduler, and
+// max-ILP stretches keyed_sigma<8> to 168 VGPRs and scratch; so at b = 8 the Makefile makes two
+// objects of this file: TMF_RAGGED_PART = 1, the embed / extract kernels under max-ILP, and
+// TMF_RAGGED_PART = 2, the keyed kernels under the default scheduler (unset: both).
 //
 // One workgroup (one wave) per strip on a flat 1-D grid.  The wave finds its frame in the
 // table's wave prefix -- blockIdx.x is wave-uniform, so the search and what it yields are scalar
-// loads and SGPRs -- and runs embed_blocks<B, false> / extract_sigmas<B, kPowerIters> on that
-// frame's one-frame view.
+// loads and SGPRs -- and runs embed_blocks<B, false> / extract_sigmas<B, kPowerIters> /
+// keyed_sigma<B, kPowerIters> on that frame's one-frame view.
+#include "tmfwm_keyed.h"
 #include "tmfwm_passes.h"
 #include "tmfwm_ragged.h"
 
 #ifndef TMF_B
 #error "TMF_B: the block size of this translation unit"
+#endif
+#ifndef TMF_RAGGED_PART
+#define TMF_RAGGED_PART 3  // bit 0: the embed / extract kernels, bit 1: the keyed kernels
 #endif
 
 namespace tmf {
@@ -35,6 +43,7 @@ TMF_DEVI RaggedFrameK *ragged_wave_frame(const RaggedArgs &r)
     return tab + ragged_find(r.nframes, blockIdx.x, [&](int i) { return tab[i].wave0; });
 }
 
+#if TMF_RAGGED_PART & 1
 template <int B>
 __global__ __launch_bounds__(64, kEmbedWaves<B>) void embed_ragged_kernel(RaggedArgs r)
 {
@@ -85,5 +94,60 @@ hipError_t extract_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st)
 
 template hipError_t embed_ragged_b<TMF_B>(const RaggedArgs &, unsigned, hipStream_t);
 template hipError_t extract_ragged_b<TMF_B>(const RaggedArgs &, unsigned, hipStream_t);
+#endif
+
+#if TMF_RAGGED_PART & 2
+// keyed extraction (tmfwm_keyed.h): keyed_sigma on the frame's one image; an undecided block goes
+// straight to the dgesdd route, a decided one through keyed_store on the one-frame view
+template <int B, bool MAP>
+TMF_DEVI void keyed_ragged_strip(const RaggedArgs &r)
+{
+    constexpr int L = Geo<B>::L, BPW = Geo<B>::BPW, LD = B + 1;
+    __shared__ float lds[BPW * B * LD];
+    const int lane = threadIdx.x & 63, g = lane / L, q = lane % L;
+    RaggedFrameK *f = ragged_wave_frame(r);
+    const KeyedArgs a = ragged_keyed_view(r, f);
+    uint32_t id;
+    const StripPos pos = ragged_strip_pos<B>(f, id);
+    float s;
+    bool ok;
+    keyed_sigma<B, kPowerIters>(a, pos, lds + g * B * LD, q, s, ok);
+    if (!pos.valid || q != 0) return;
+    if (!ok) {
+        a.fb_list[atomicAdd(a.fb_count, 1u)] = id;
+        return;
+    }
+    keyed_store<MAP>(a, 0, pos.bi, pos.bj, s);
+}
+
+template <int B>
+__global__ __launch_bounds__(64, kKeyedWaves<B>) void sigma1_map_ragged_kernel(RaggedArgs r)
+{
+    keyed_ragged_strip<B, true>(r);
+}
+
+template <int B>
+__global__ __launch_bounds__(64, kKeyedWaves<B>) void extract_keyed_ragged_kernel(RaggedArgs r)
+{
+    keyed_ragged_strip<B, false>(r);
+}
+
+template <int B>
+hipError_t sigma1_map_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st)
+{
+    hipLaunchKernelGGL((sigma1_map_ragged_kernel<B>), dim3(waves), dim3(64), 0, st, r);
+    return hipGetLastError();
+}
+
+template <int B>
+hipError_t extract_keyed_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st)
+{
+    hipLaunchKernelGGL((extract_keyed_ragged_kernel<B>), dim3(waves), dim3(64), 0, st, r);
+    return hipGetLastError();
+}
+
+template hipError_t sigma1_map_ragged_b<TMF_B>(const RaggedArgs &, unsigned, hipStream_t);
+template hipError_t extract_keyed_ragged_b<TMF_B>(const RaggedArgs &, unsigned, hipStream_t);
+#endif
 
 }  // namespace tmf

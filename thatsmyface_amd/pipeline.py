@@ -19,6 +19,10 @@ Results come back in input order and are byte-identical to
 ``embed_watermark(img, watermark_data, preserve_ratio)`` followed by
 ``img.save(format="PNG")`` per image.  The device stage is a parameter so the
 pipeline logic is testable on CPU (tests/test_pipeline.py).
+
+``extract_images`` is the extraction counterpart for a verifier that stores keys instead of
+originals: decode on the worker threads, then per group of ``batch_images`` images of any
+sizes one upload, one ``extract_keyed_ragged`` and one copy back (``KeyedExtractStage``).
 """
 from __future__ import annotations
 
@@ -167,6 +171,140 @@ class RaggedGpuStage(GpuStage):
             _e.synchronize()
 
         return [(ho.numpy(), wait) for ho in host_out]
+
+
+def _check_key(i: int, key, h: int, w: int, block: int) -> None:
+    """What watermarking.extract_watermark_keyed asks of a key, for image i of h x w pixels."""
+    if not isinstance(key, np.ndarray) or key.dtype != np.float32:
+        raise TypeError(f"keys[{i}] must be a float32 numpy array (extraction_key's result), got {getattr(key, 'dtype', type(key))}")
+    if key.shape != (h // block, w // block):
+        raise ValueError(f"keys[{i}] shape {key.shape} != ({h // block}, {w // block}) for a {w}x{h} image at block size {block}: "
+                         "a key belongs to one block size and one image size")
+
+
+class KeyedExtractStage:
+    """Batched device stage of ``extract_images``: a group of decoded watermarked images of any
+    sizes and their keys go up in one copy (a key that several images share goes up once), one
+    ``extract_keyed_ragged`` extracts the whole group, and the tiles come back in one copy.
+
+    Called as ``stage(rgbs, keys, indices)``; returns one ``(tile, wait)`` per image, in the
+    group's order, where ``wait()`` blocks until the copy back has landed.  An image smaller
+    than a block has no block: its tile is empty and it takes no part in the device call."""
+
+    def __init__(self, block: int, alpha: float, device=None, route: str = SVD_ROUTE):
+        import torch
+
+        from . import batch
+
+        self.torch, self.batch = torch, batch
+        self.block, self.alpha, self.route = int(block), float(alpha), route
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.stream = torch.cuda.Stream(device=self.device)
+
+    def __call__(self, rgbs, keys, indices):
+        torch, b = self.torch, self.block
+        live = [j for j, rgb in enumerate(rgbs) if rgb.shape[0] >= b and rgb.shape[1] >= b]
+        tiles = [np.zeros((rgb.shape[0] // b, rgb.shape[1] // b), np.uint8) for rgb in rgbs]
+        if not live:
+            return [(t, None) for t in tiles]
+        # one pinned buffer for the group's pixels and keys (16-byte aligned pieces), one for its tiles
+        pieces, rgb_at, key_at, total = [], {}, {}, 0
+        for j in live:
+            for arr, at, name in ((rgbs[j], rgb_at, j), (keys[j], key_at, id(keys[j]))):
+                if name not in at:
+                    at[name] = total
+                    pieces.append((total, arr))
+                    total += (arr.nbytes + 15) & ~15
+        host_in = torch.empty((total,), dtype=torch.uint8, pin_memory=True)
+        flat = host_in.numpy()
+        for off, arr in pieces:
+            flat[off:off + arr.nbytes] = np.ascontiguousarray(arr).reshape(-1).view(np.uint8)
+        out_at, out_total = [], 0
+        for j in live:
+            out_at.append(out_total)
+            out_total += (tiles[j].size + 15) & ~15
+        host_out = torch.empty((out_total,), dtype=torch.uint8, pin_memory=True)
+        with torch.cuda.stream(self.stream):
+            dev_in = host_in.to(self.device, non_blocking=True)
+            dev_out = torch.empty((out_total,), dtype=torch.uint8, device=self.device)
+            frames, dkeys, outs = [], [], []
+            for j, o in zip(live, out_at):
+                h, w = rgbs[j].shape[:2]
+                nbh, nbw = h // b, w // b
+                at = rgb_at[j]
+                frames.append(dev_in[at:at + h * w * 3].view(h, w, 3))
+                k0 = key_at[id(keys[j])]
+                dkeys.append(dev_in[k0:k0 + 4 * nbh * nbw].view(torch.float32).view(nbh, nbw))
+                outs.append(dev_out[o:o + nbh * nbw].view(nbh, nbw))
+            self.batch.extract_keyed_ragged(frames, dkeys, b, self.alpha, out=outs, stream=self.stream, route=self.route)
+            host_out.copy_(dev_out, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(self.stream)
+        keep = (dev_in, dev_out, host_in)  # alive until the copy back has landed
+
+        def wait(_e=done, _k=keep):
+            _e.synchronize()
+
+        res = host_out.numpy()
+        for j, o in zip(live, out_at):
+            tiles[j] = res[o:o + tiles[j].size].reshape(tiles[j].shape)
+        return [(t, wait if j in live else None) for j, t in enumerate(tiles)]
+
+
+def extract_images(images: Iterable, keys: Sequence, custom_settings: dict | None = None, batch_images: int = 16,
+                   workers: int | None = None, device_stage: Callable | None = None):
+    """The extraction counterpart of ``embed_images`` for a verifier that stores keys
+    (``watermarking.extraction_key``) instead of originals: yields, in input order, the
+    (W/b) x (H/b) mode-"L" extracted watermark of every watermarked image (bytes, file object or
+    PIL image) against ``keys[i]``, pixel for pixel ``extract_watermark_keyed(images[i], keys[i],
+    custom_settings)``.  The same key array may stand for several images.
+
+    Images are decoded on worker threads and taken ``batch_images`` at a time, of any sizes:
+    each group is one upload, one ``extract_keyed_ragged`` and one copy back
+    (``KeyedExtractStage``; a custom ``device_stage`` is called as ``stage(rgbs, keys, indices)``
+    and returns one ``(tile, wait)`` per image).  A key that is not float32 (TypeError) or whose
+    shape does not fit its image (ValueError) raises before any device work for its group.
+    Decoding the tiles' QR content stays with the caller (``qrcode_generator.qrcode_to_text``)."""
+    settings = custom_settings or {}
+    block = int(settings.get("block_size", BLOCK_SIZE))
+    alpha = float(settings.get("alpha", ALPHA))
+    route = settings.get("svd_route") or os.environ.get("TMFWM_SVD_ROUTE") or SVD_ROUTE  # as watermarking._route
+    sources: Sequence = list(images)
+    keys = list(keys)
+    if len(keys) != len(sources):
+        raise ValueError(f"{len(keys)} keys for {len(sources)} images")
+    if batch_images is None or int(batch_images) < 1:
+        raise ValueError(f"batch_images must be >= 1, got {batch_images!r}")
+    if block <= 0:
+        raise ValueError(f"block_size must be positive, got {block}")
+    stage = device_stage or KeyedExtractStage(block, alpha, route=route)
+    n_workers = workers or min(16, max(2, (len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 4)))
+
+    def finish(results):
+        for tile, wait in results:
+            if wait is not None:
+                wait()
+            yield Image.fromarray(tile)
+
+    def run():
+        with ThreadPoolExecutor(n_workers, thread_name_prefix="tmf-io") as pool:
+            decoded: list[Future] = [pool.submit(_decode, s) for s in sources]
+            pending = None  # the group on the device while the next one is checked and uploaded
+            for i0 in range(0, len(decoded), int(batch_images)):
+                indices = list(range(i0, min(i0 + int(batch_images), len(decoded))))
+                rgbs = [decoded[i].result() for i in indices]
+                for i, rgb in zip(indices, rgbs):
+                    _check_key(i, keys[i], rgb.shape[0], rgb.shape[1], block)
+                results = stage(rgbs, [keys[i] for i in indices], indices)
+                if len(results) != len(indices):
+                    raise ValueError(f"the device stage returned {len(results)} results for {len(indices)} images")
+                if pending is not None:
+                    yield from finish(pending)
+                pending = results
+            if pending is not None:
+                yield from finish(pending)
+
+    return run()
 
 
 def embed_images(images: Iterable, watermark_data, preserve_ratio: bool = True, custom_settings: dict | None = None,

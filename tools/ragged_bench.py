@@ -10,12 +10,18 @@ Workload B (the cost of the frame table and of going without the list pass): 256
 1920 x 1080 at b = 8 and b = 16, on noise covers and on camera-like covers; embed_ragged against
 embed_batch (a tile per frame) on the same frames.
 
+Workload K (ragged keyed extraction): workload A's frames, embedded once, with their
+keys resident on the device.  Three comparisons: extract_keyed_ragged against the loop of 64
+single-frame extract_keyed calls; extract_keyed_ragged against extract_ragged with the originals
+(the pair path; its time is reported as "base"); sigma1_map_ragged against the loop of 64
+single-frame sigma1_map calls.
+
 Both arms of a comparison run alternately in one process, each timing a window of `inner` calls
 that ends in a device synchronise.  Every ratio comes with the A/A spread of its own run: the
 medians of the even and of the odd rounds of the same arm, as a ratio.  The arms' outputs are
 compared byte for byte before anything is timed.
 
-usage: python tools/ragged_bench.py [--workload a|b|ab] [--rounds R] [--frames-b N]
+usage: python tools/ragged_bench.py [--workload a|b|k|ab|abk] [--rounds R] [--frames-b N]
 """
 import argparse
 import json
@@ -64,12 +70,18 @@ def compare(name, arms, inner, rounds, extra):
     return rec
 
 
-def workload_a(rounds, dev):
-    b, alpha, n = 8, 0.1, 64
+def frames_a(dev, b, n):
+    """Workload A's covers and tiles: (picks, frames, tiles)."""
     rng = np.random.default_rng(20240)
     picks = [SIZES[int(k)] for k in rng.integers(0, len(SIZES), n)]
     frames = [batch.synth_photo_frames(1, h, w, seed=7000 + i, device=dev)[0].contiguous() for i, (h, w) in enumerate(picks)]
     tiles = [batch.synth_qr_tile(h // b, w // b, seed=8000 + i, device=dev) for i, (h, w) in enumerate(picks)]
+    return picks, frames, tiles
+
+
+def workload_a(rounds, dev):
+    b, alpha, n = 8, 0.1, 64
+    picks, frames, tiles = frames_a(dev, b, n)
     frames1 = [f[None] for f in frames]
     state = {}
 
@@ -92,6 +104,40 @@ def workload_a(rounds, dev):
     return compare("A", {"base": loop, "ragged": ragged}, 10, rounds,
                    {"what": "64 images embed+extract: ragged vs loop of single-frame calls", "block": b, "megapixels": round(mp, 1),
                     "sizes": sizes, "outputs_equal": True})
+
+
+def workload_k(rounds, dev):
+    b, alpha, n = 8, 0.1, 64
+    picks, frames, tiles = frames_a(dev, b, n)
+    wm = batch.embed_ragged(frames, tiles, b, alpha)
+    frames1, wm1 = [f[None] for f in frames], [w[None] for w in wm]
+    keys = batch.sigma1_map_ragged(frames, b)
+    state = {}
+    arms = {
+        "keyed_loop": lambda: state.__setitem__("keyed_loop", [batch.extract_keyed(w, k, b, alpha) for w, k in zip(wm1, keys)]),
+        "keyed_ragged": lambda: state.__setitem__("keyed_ragged", batch.extract_keyed_ragged(wm, keys, b, alpha)),
+        "pair_ragged": lambda: state.__setitem__("pair_ragged", batch.extract_ragged(wm, frames, b, alpha)),
+        "map_loop": lambda: state.__setitem__("map_loop", [batch.sigma1_map(f, b) for f in frames1]),
+        "map_ragged": lambda: state.__setitem__("map_ragged", batch.sigma1_map_ragged(frames, b)),
+    }
+    for fn in arms.values():
+        fn()
+    torch.cuda.synchronize()
+    for i in range(n):
+        assert torch.equal(state["keyed_loop"][i][0], state["keyed_ragged"][i]), ("keyed extract differs from the loop", i)
+        assert torch.equal(state["pair_ragged"][i], state["keyed_ragged"][i]), ("keyed extract differs from the pair path", i)
+        assert torch.equal(state["map_loop"][i][0].view(torch.int32), state["map_ragged"][i].view(torch.int32)), ("key differs", i)
+    sm, sx = {}, {}
+    batch.sigma1_map_ragged(frames, b, stats=sm)
+    batch.extract_keyed_ragged(wm, keys, b, alpha, stats=sx)
+    extra = {"block": b, "megapixels": round(sum(h * w for h, w in picks) / 1e6, 1), "outputs_equal": True,
+             "lapack_blocks_map": sm["lapack_blocks"], "lapack_blocks_extract": sx["lapack_blocks"]}
+    return [compare("K1", {"base": arms["keyed_loop"], "ragged": arms["keyed_ragged"]}, 10, rounds,
+                    {"what": "64 images keyed extract: extract_keyed_ragged vs loop of single-frame extract_keyed", **extra}),
+            compare("K2", {"base": arms["pair_ragged"], "ragged": arms["keyed_ragged"]}, 10, rounds,
+                    {"what": "64 images extract: extract_keyed_ragged vs extract_ragged with the originals (base)", **extra}),
+            compare("K3", {"base": arms["map_loop"], "ragged": arms["map_ragged"]}, 10, rounds,
+                    {"what": "64 images key maps: sigma1_map_ragged vs loop of single-frame sigma1_map", **extra})]
 
 
 def workload_b(rounds, dev, n):
@@ -127,7 +173,7 @@ def workload_b(rounds, dev, n):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", default="ab", choices=("a", "b", "ab"))
+    ap.add_argument("--workload", default="ab", choices=("a", "b", "k", "ab", "abk"))
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--frames-b", type=int, default=256)
     a = ap.parse_args()
@@ -139,6 +185,8 @@ def main():
         workload_a(a.rounds, dev)
     if "b" in a.workload:
         workload_b(a.rounds, dev, a.frames_b)
+    if "k" in a.workload:
+        workload_k(a.rounds, dev)
 
 
 if __name__ == "__main__":

@@ -28,7 +28,11 @@ def units(csrc):
     for path in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
         tu = os.path.basename(path)
         if tu in PER_SIZE:
-            out += [(tu, ["-DTMF_B=%d" % b] + (ILP if (tu, b) == ("tmfwm_ragged_strip.hip", 8) else [])) for b in SIZES]
+            for b in SIZES:
+                if (tu, b) == ("tmfwm_ragged_strip.hip", 8):  # two objects: embed / extract under max-ILP, the keyed kernels not
+                    out += [(tu, ["-DTMF_B=8", "-DTMF_RAGGED_PART=1"] + ILP), (tu, ["-DTMF_B=8", "-DTMF_RAGGED_PART=2"])]
+                else:
+                    out.append((tu, ["-DTMF_B=%d" % b]))
         else:
             out.append((tu, ILP if tu == "tmfwm_embed8.hip" else []))
     return out + [("tmfwm_capi.cpp", ["-x", "hip"]), ("tmfwm_multi.cpp", ["-x", "hip"])]
