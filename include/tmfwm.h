@@ -318,6 +318,54 @@ int tmfwm_sigma1_map_ragged(const tmfwm_key_frame *frames, int64_t n_frames, int
 int tmfwm_extract_keyed_ragged(const tmfwm_keyed_frame *frames, int64_t n_frames, int32_t block, double alpha,
                                int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
 
+/*
+ * Embed that also returns the extraction key (added within ABI 10; the version number is
+ * unchanged and existing entry points keep their behaviour): the enrolment side of keyed
+ * extraction in one call.  `out` receives exactly tmfwm_embed_route's bytes (per-frame tiles as
+ * tmfwm_embed_tiles: frame f's tile at wm_tiles + f * tile_stride, 0 = one shared tile) and
+ * out_key exactly tmfwm_sigma1_map's key of the ORIGINAL frames `rgb` -- the key that
+ * tmfwm_extract_keyed takes with the frames in `out`.  The key depends on neither alpha nor the
+ * tiles nor the route.
+ *
+ * On TMFWM_ROUTE_HYBRID and TMFWM_ROUTE_REFERENCE the key comes out of the embed passes: the embed
+ * kernels already hold sigma_1 of every block and store f32(sigma_1) where its certified
+ * enclosure is one float; a block where it is not (about 2^-20 of them) joins the dgesdd-route
+ * blocks, whose pass stores its own S[0], so *n_lapack_blocks may exceed tmfwm_embed_route's by
+ * those blocks.  On the rank-1 routes the call runs tmfwm_embed_route's passes and then
+ * tmfwm_sigma1_map's on the same stream, and *n_lapack_blocks and
+ * tmfwm_last_list_pass_blocks() are the sums over both.
+ *
+ * key_stride: bytes between consecutive frames' keys, a multiple of 4 and
+ * >= (height/block)*(width/block)*4 (TMFWM_ERR_INVALID otherwise); ignored for n_frames == 1.
+ * Bytes of a padded stride outside the keys are not written.  out_key must be 4-byte aligned and,
+ * with TMFWM_MEM_DEVICE, disjoint from rgb, wm_tiles and out (TMFWM_ERR_INVALID otherwise).  A
+ * frame size without a block gets its colour round trip and no key entry (out_key is not looked
+ * at).  Memory kinds (TMFWM_MEM_HOST stages the keys back with the pixels), chunking, the count
+ * and the non-convergence report as tmfwm_embed_route.  Pixels are 3 bytes (TMFWM_PIX_RGB).
+ */
+int tmfwm_embed_key(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
+                    const uint8_t *wm_tiles, int64_t tile_stride, int32_t block, double alpha, uint8_t *out,
+                    float *out_key, int64_t key_stride, int32_t mem_kind, void *hip_stream, int32_t route,
+                    int64_t *n_lapack_blocks);
+
+/*
+ * The same over a ragged batch: tmfwm_embed_ragged's frames, each with a key output.  Frame i's
+ * `out` bytes are tmfwm_embed_ragged's and its key bits tmfwm_sigma1_map_ragged's.  Descriptors,
+ * memory kinds, routes (TMFWM_ROUTE_HYBRID and TMFWM_ROUTE_REFERENCE), the count and the checks as
+ * tmfwm_embed_ragged; every `out` and every `out_key` must be disjoint from every input of the
+ * call and from every other output (TMFWM_ERR_INVALID otherwise), and every out_key 4-byte
+ * aligned.  A frame without a block gets its colour round trip; its out_key is not looked at.
+ */
+typedef struct {
+    const uint8_t *rgb;      /* height x width x 3, packed rows: the original */
+    uint8_t *out;            /* same shape: the watermarked frame */
+    const uint8_t *wm_tile;  /* (height/block) x (width/block), packed */
+    float *out_key;          /* (height/block) x (width/block) float32, packed */
+    int32_t height, width;
+} tmfwm_embed_key_frame;     /* 40 bytes */
+int tmfwm_embed_key_ragged(const tmfwm_embed_key_frame *frames, int64_t n_frames, int32_t block, double alpha,
+                           int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
+
 /* tmfwm_extract_route with a pixel layout and frame stride per input image (ABI 8). */
 int tmfwm_extract_px(const uint8_t *wm_rgb, int32_t wm_pixel_bytes, int64_t wm_frame_stride, const uint8_t *orig_rgb,
                      int32_t orig_pixel_bytes, int64_t orig_frame_stride, int64_t n_frames, int32_t height, int32_t width,

@@ -87,6 +87,13 @@ class KeyedFrame(ctypes.Structure):
                 ("height", ctypes.c_int32), ("width", ctypes.c_int32)]
 
 
+class EmbedKeyFrame(ctypes.Structure):
+    """tmfwm_embed_key_frame: one frame of tmfwm_embed_key_ragged (include/tmfwm.h)."""
+
+    _fields_ = [("rgb", ctypes.c_void_p), ("out", ctypes.c_void_p), ("wm_tile", ctypes.c_void_p), ("out_key", ctypes.c_void_p),
+                ("height", ctypes.c_int32), ("width", ctypes.c_int32)]
+
+
 class TileJob(ctypes.Structure):
     """tmfwm_tile_job: one job of tmfwm_prepare_tiles_ragged (include/tmfwm.h)."""
 
@@ -115,6 +122,8 @@ SIGNATURES = {
     "tmfwm_extract_ragged": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _VP, _I32, _VP]),
     "tmfwm_sigma1_map_ragged": (ctypes.c_int, [_VP, _I64, _I32, _I32, _VP, _I32, _VP]),
     "tmfwm_extract_keyed_ragged": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _VP, _I32, _VP]),
+    "tmfwm_embed_key": (ctypes.c_int, [_VP, _I64, _I32, _I32, _I64, _VP, _I64, _I32, _D, _VP, _VP, _I64, _I32, _VP, _I32, _VP]),
+    "tmfwm_embed_key_ragged": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _VP, _I32, _VP]),
     "tmfwm_extract_px": (ctypes.c_int, [_VP, _I32, _I64, _VP, _I32, _I64, _I64, _I32, _I32, _I32, _D, _VP, _I32, _VP, _I32, _VP]),
     "tmfwm_embed_multi": (ctypes.c_int, [_VP, _I64, _I32, _I32, _I64, _VP, _I32, _D, _VP, _VP, _I32, _VP]),
     "tmfwm_release_cached_buffers": (ctypes.c_int, []),

@@ -171,6 +171,49 @@ def extract_keyed(wframes: torch.Tensor, key: torch.Tensor, block: int = 8, alph
     return out
 
 
+def embed_with_key(frames: torch.Tensor, wm_tile: torch.Tensor, block: int = 8, alpha: float = 0.1,
+                   out: torch.Tensor | None = None, key_out: torch.Tensor | None = None, stream=None,
+                   stats: dict | None = None, route: str = "hybrid"):
+    """embed_batch that also returns the extraction key of the ORIGINAL frames, in one call
+    (tmfwm_embed_key): (out, key), out the bytes of embed_batch(frames, wm_tile, ...), key the
+    float32 (N, H//b, W//b) bits of sigma1_map(frames, block) -- what extract_keyed takes with
+    `out`.  On the hybrid and reference routes the key comes out of the embed passes themselves
+    (DESIGN.md 5); on the rank-1 routes the call runs the map's passes after the embed's.
+    wm_tile, stats and route as embed_batch's; "lapack_blocks" counts a block whose key the
+    dgesdd route had to decide as well."""
+    _check_frames(frames, "frames")
+    n, h, w, _ = frames.shape
+    if block not in SUPPORTED_BLOCK_SIZES:
+        raise NotImplementedError(f"block {block}")
+    nbh, nbw = h // block, w // block
+    if tuple(wm_tile.shape) not in ((nbh, nbw), (n, nbh, nbw)) or wm_tile.dtype != torch.uint8 or not wm_tile.is_cuda:
+        raise ValueError(f"wm_tile must be ({nbh}, {nbw}) or ({n}, {nbh}, {nbw}) uint8 on the GPU, got {tuple(wm_tile.shape)}")
+    wm_tile = wm_tile.contiguous()
+    if out is None:
+        out = torch.empty_like(frames)
+    else:
+        _check_frames(out, "out")
+        if out.shape != frames.shape:
+            raise ValueError("out shape mismatch")
+    shape = (n, nbh, nbw)
+    if key_out is None:
+        key_out = torch.empty(shape, dtype=torch.float32, device=frames.device)
+    elif (not isinstance(key_out, torch.Tensor) or tuple(key_out.shape) != shape or key_out.dtype != torch.float32
+          or key_out.device != frames.device or not key_out.is_contiguous()):
+        raise ValueError(f"key_out must be {shape} float32, contiguous, on the frames' device")
+    cnt, ptr = _count_ptr(stats)
+    with torch.cuda.device(frames.device):
+        L = _lib.load()
+        _lib.check(L.tmfwm_embed_key(frames.data_ptr(), n, h, w, h * w * 3, wm_tile.data_ptr(),
+                                     0 if wm_tile.dim() == 2 else nbh * nbw, block, float(alpha), out.data_ptr(),
+                                     key_out.data_ptr(), nbh * nbw * 4, _lib.MEM_DEVICE, _stream(stream), _lib.route_code(route), ptr),
+                   "embed_with_key")
+    if stats is not None:
+        stats["lapack_blocks"] = int(cnt.value)
+        stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks())
+    return out, key_out
+
+
 def _check_ragged(frames, name: str, device=None):
     """A sequence of (H_i, W_i, 3) uint8 contiguous GPU tensors on one device -> (list, device)."""
     frames = list(frames)
@@ -204,17 +247,8 @@ def _ragged_route(route) -> int:
     return code
 
 
-def embed_ragged(frames, tiles, block: int = 8, alpha: float = 0.1, out=None, stream=None, stats: dict | None = None,
-                 route: str = "hybrid") -> list:
-    """Embed frames of mixed sizes, each with its own tile, by one set of launches
-    (tmfwm_embed_ragged): frames[i] is (H_i, W_i, 3) uint8, tiles[i] (H_i // block, W_i // block)
-    uint8, all contiguous on one GPU.  Returns the outputs as per-frame views of one device
-    allocation (or `out`, a sequence of tensors shaped like the frames); output i is the bytes
-    of embed_batch(frames[i][None], tiles[i], ...)[0].  A frame smaller than a block gets its
-    colour round trip.  stats and route ("hybrid" / "reference") as embed_batch's; no list pass
-    runs, so "list_pass_blocks" is 0."""
-    import ctypes
-
+def _embed_ragged_args(frames, tiles, block, route, out):
+    """embed_ragged's checks and output views: (frames, tiles, out, device, route code)."""
     if block not in SUPPORTED_BLOCK_SIZES:
         raise NotImplementedError(f"block {block}")
     code = _ragged_route(route)
@@ -233,6 +267,21 @@ def embed_ragged(frames, tiles, block: int = 8, alpha: float = 0.1, out=None, st
         out, _ = _check_ragged(out, "out", dev)
         if len(out) != len(frames) or any(o.shape != f.shape for o, f in zip(out, frames)):
             raise ValueError("out must hold one tensor per frame, shaped like it")
+    return frames, tiles, out, dev, code
+
+
+def embed_ragged(frames, tiles, block: int = 8, alpha: float = 0.1, out=None, stream=None, stats: dict | None = None,
+                 route: str = "hybrid") -> list:
+    """Embed frames of mixed sizes, each with its own tile, by one set of launches
+    (tmfwm_embed_ragged): frames[i] is (H_i, W_i, 3) uint8, tiles[i] (H_i // block, W_i // block)
+    uint8, all contiguous on one GPU.  Returns the outputs as per-frame views of one device
+    allocation (or `out`, a sequence of tensors shaped like the frames); output i is the bytes
+    of embed_batch(frames[i][None], tiles[i], ...)[0].  A frame smaller than a block gets its
+    colour round trip.  stats and route ("hybrid" / "reference") as embed_batch's; no list pass
+    runs, so "list_pass_blocks" is 0."""
+    import ctypes
+
+    frames, tiles, out, dev, code = _embed_ragged_args(frames, tiles, block, route, out)
     desc = (_lib.EmbedFrame * max(len(frames), 1))()
     for i, (f, t, o) in enumerate(zip(frames, tiles, out)):
         desc[i] = _lib.EmbedFrame(f.data_ptr(), o.data_ptr(), t.data_ptr(), f.shape[0], f.shape[1])
@@ -336,6 +385,39 @@ def sigma1_map_ragged(frames, block: int = 8, out=None, stream=None, stats: dict
         stats["lapack_blocks"] = int(cnt.value)
         stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks()) if frames else 0
     return list(out)
+
+
+def embed_with_key_ragged(frames, tiles, block: int = 8, alpha: float = 0.1, out=None, key_out=None, stream=None,
+                          stats: dict | None = None, route: str = "hybrid"):
+    """embed_ragged that also returns every frame's extraction key, by one set of launches
+    (tmfwm_embed_key_ragged): (outs, keys), outs[i] the bytes of embed_ragged's output i, keys[i]
+    the float32 (H_i // block, W_i // block) bits of sigma1_map_ragged's key i -- the key of the
+    original frames[i], what extract_keyed_ragged takes with outs[i].  out and key_out are optional
+    sequences of caller tensors (as embed_ragged's out and sigma1_map_ragged's out).  A frame
+    smaller than a block gets its colour round trip and an empty key.  stats and route as
+    embed_ragged's."""
+    import ctypes
+
+    frames, tiles, out, dev, code = _embed_ragged_args(frames, tiles, block, route, out)
+    shapes = [(f.shape[0] // block, f.shape[1] // block) for f in frames]
+    if key_out is None:  # float32 views of one uint8 allocation: its pieces start on 16-byte boundaries
+        keys = [v.view(torch.float32).view(shapes[i]) for i, v in enumerate(
+            _ragged_views([4 * a * b for a, b in shapes], lambda i: (4 * shapes[i][0] * shapes[i][1],), dev))] if frames else []
+    else:
+        keys = _check_ragged_out(key_out, shapes, torch.float32, dev, "key")
+    desc = (_lib.EmbedKeyFrame * max(len(frames), 1))()
+    for i, (f, t, o, k) in enumerate(zip(frames, tiles, out, keys)):
+        desc[i] = _lib.EmbedKeyFrame(f.data_ptr(), o.data_ptr(), t.data_ptr(), k.data_ptr(), f.shape[0], f.shape[1])
+    cnt, ptr = _count_ptr(stats)
+    L = _lib.load()
+    if frames:
+        with torch.cuda.device(dev):
+            _lib.check(L.tmfwm_embed_key_ragged(ctypes.addressof(desc), len(frames), block, float(alpha), _lib.MEM_DEVICE,
+                                                _stream(stream), code, ptr), "embed_with_key_ragged")
+    if stats is not None:
+        stats["lapack_blocks"] = int(cnt.value)
+        stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks()) if frames else 0
+    return list(out), list(keys)
 
 
 def extract_keyed_ragged(wframes, keys, block: int = 8, alpha: float = 0.1, out=None, stream=None, stats: dict | None = None,

@@ -10,6 +10,7 @@
 
 #include "tmfwm_device.h"
 #include "tmfwm_colour_tail.h"
+#include "tmfwm_embed_key.h"
 #include "tmfwm_internal.h"
 
 namespace tmf {
@@ -337,7 +338,10 @@ constexpr bool kPinChain = B == 10 || B == 14;
 
 // One wave's blocks: strip mode (LIST = false: the strip of blockIdx) or list mode (pos and
 // id from the slow list).  id = (frame * nbh + bi) * nbw + bj, relative to a.src.
-template <int B, bool LIST>
+// KEY (tmfwm_embed_key.h): the block's key entry, f32(sigma_1) of its DCT block, goes
+// to a.key_out where the pre-blend ends of sigma_1 decide it, and the block to the dgesdd route
+// where they do not.  A compile-time variant: the plain kernels keep their code.
+template <int B, bool LIST, bool KEY = false>
 TMF_DEVI void embed_blocks(const EmbedArgs &a, const StripPos &pos, uint32_t id, float *lds, float *lds2)
 {
     constexpr int L = Geo<B>::L, R = Geo<B>::R, LD = B + 1, NW = Geo<B>::NW, TS = kEmbedTS<B>;
@@ -510,6 +514,17 @@ TMF_DEVI void embed_blocks(const EmbedArgs &a, const StripPos &pos, uint32_t id,
                 rk[k] += ge;
                 rk[j] += 1 - ge;
             }
+    }
+    // KEY: the top triplet's sigma is s1 itself, so its pre-blend ends (the S' ends below, before
+    // the blend) are formed here from s1 and tE, the same on every lane of the block.  One float:
+    // lane q == 0 stores the entry (a block left to the list pass gets it there).  Two: the block
+    // joins the dgesdd-route list, whose pass stores its S[0].
+    bool kund = false;
+    if constexpr (KEY) {
+        const KeyDecision d = embed_key_of(s1, tE);
+        kund = !d.decided;
+        if (d.decided && q == 0 && pos.valid && !slow)
+            a.key_out[pos.frame * a.key_stride + (int64_t)pos.bi * a.nbw + pos.bj] = d.key;
     }
     // U = A / sigma as f32 intervals [f32(u - E), f32(u + E)]; triplets that do not reach the
     // output (f32(sigma) == 0) take U = [2, 2] against B = [-2 S', 2 S'] (|f32 entries| <= 1)
@@ -771,7 +786,7 @@ TMF_DEVI void embed_blocks(const EmbedArgs &a, const StripPos &pos, uint32_t id,
         }
     }
     // the dgesdd route (embed_fixup_kernel) redoes flagged blocks and blocks with an undecided byte
-    const bool fix = flag20 || (cert && mixed) || group_or<L>(unc && cert ? 1 : 0) != 0;
+    const bool fix = flag20 || (cert && mixed) || group_or<L>(unc && cert ? 1 : 0) != 0 || kund;
     if (fix && pos.valid && !slow && q == 0) a.fb_list[atomicAdd(a.fb_count, 1u)] = id;
     stamp(6);
 }
@@ -807,6 +822,41 @@ __global__ __launch_bounds__(64, kEmbedWaves<B>) void embed_kernel(EmbedArgs a)
         const StripPos pos = strip_pos<B>(a.strips_per_row, a.nbw);
         const uint32_t id = (uint32_t)(((int64_t)blockIdx.y * a.nbh + pos.bi) * a.nbw + pos.bj);
         embed_blocks<B, false>(a, pos, id, lds, lds2);
+    }
+}
+
+// The key variant (a.key_out set): embed_kernel with embed_blocks<B, LIST, true>.  The body is
+// written out a second time: with both kernels calling one device function for it,
+// embed_kernel<8> compiled to 256 VGPRs and 56 bytes of scratch instead of 255 and none.
+template <int B, bool LIST = false>
+__global__ __launch_bounds__(64, kEmbedWaves<B>) void embed_key_kernel(EmbedArgs a)
+{
+    constexpr int L = Geo<B>::L, BPW = Geo<B>::BPW, TS = kEmbedTS<B>;
+    __shared__ __attribute__((aligned(16))) float lds_all[BPW * TS + kHiPad<B> + kLds2Floats<B>];
+    float *lds = lds_all, *lds2 = lds_all + BPW * TS + kHiPad<B>;
+    if constexpr (LIST) {
+        // grid-stride over the slow list's segments (their lengths are known on the device only)
+        const uint32_t per_frame = (uint32_t)a.nbh * (uint32_t)a.nbw, rows = (uint32_t)a.nframes * (uint32_t)a.nbh;
+        const int g = (threadIdx.x & 63) / L;
+        for (uint32_t s = blockIdx.x; s < kListShards; s += gridDim.x) {
+            const uint32_t n = a.slow_shards[s * kShardStride], base = shard_base(s, rows, (uint32_t)a.nbw);
+            if (n != 0 && (threadIdx.x & 63) == 0) atomicAdd(a.slow_count, n);
+            for (uint32_t t0 = 0; t0 < n; t0 += BPW) {
+                StripPos pos;
+                pos.valid = t0 + g < n;
+                const uint32_t id = pos.valid ? a.slow_list[base + t0 + g] : 0u;
+                pos.frame = id / per_frame;
+                const uint32_t rem = id % per_frame;
+                pos.bi = (int)(rem / (uint32_t)a.nbw);
+                pos.bj = (int)(rem % (uint32_t)a.nbw);
+                embed_blocks<B, true, true>(a, pos, id, lds, lds2);
+                __syncthreads();  // the LDS tiles are reused by the next listed blocks
+            }
+        }
+    } else {
+        const StripPos pos = strip_pos<B>(a.strips_per_row, a.nbw);
+        const uint32_t id = (uint32_t)(((int64_t)blockIdx.y * a.nbh + pos.bi) * a.nbw + pos.bj);
+        embed_blocks<B, false, true>(a, pos, id, lds, lds2);
     }
 }
 

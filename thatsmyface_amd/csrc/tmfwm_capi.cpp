@@ -447,23 +447,56 @@ void clear_error() { t_err.clear(); }
 
 int check_frames(int64_t n, int32_t H, int32_t W, int64_t stride, int32_t block) { return ::check_frames(n, H, W, stride, block); }
 
-// Both passes of embed over device-resident frames (a.src / a.dst / a.wm set).
+// the embed call also wants the key (a.key_out) and its passes do not store it themselves: on the
+// rank-1 routes (the pre-pass is not fused) and at a size whose key variant is not built
+// (tmfwm_embed_key.h) the call runs the map's passes after the embed's
+bool embed_key_composed(int block, int route, bool key)
+{
+    const bool pre = (route == TMFWM_ROUTE_RANK1 || route == TMFWM_ROUTE_RANK1_REFERENCE) && rank1_block(block);
+    return key && (pre || !embed_key_fused(block));
+}
+
+KeyedArgs keyed_args(int64_t n, int32_t H, int32_t W, int64_t stride, int32_t block, double alpha);
+bool dev_aligned(const void *p, const void *q, int64_t stride, int W);
+
+// Both passes of embed over device-resident frames (a.src / a.dst / a.wm set).  With a.key_out
+// the key of the frames in a.src as well: out of the key variants of the same
+// passes, or -- composed -- by the map's passes over chunks of their own after the embed's, on
+// the same stream and through the same driver, so that the counts are the sums over both.
 int run_embed(const EmbedArgs &a, hipStream_t st, const Report &rep, int route)
 {
     Chunks ch;
     ch.plan(a.nframes, (int64_t)a.nbh * a.nbw);
-    if (ch.cap == 0) TMF_HIP(launch_embed(a, st));  // no full block: the colour round trip only, zero counts
+    if (ch.cap == 0) TMF_HIP(launch_embed(a, st));  // no full block: the colour round trip only, zero counts, no key entry
     const bool pre = (route == TMFWM_ROUTE_RANK1 || route == TMFWM_ROUTE_RANK1_REFERENCE) && rank1_block(a.block);
-    const bool list_pass = (embed_defers(a.block) && route != TMFWM_ROUTE_REFERENCE && route != TMFWM_ROUTE_RANK1_REFERENCE) ||
-                           (route == TMFWM_ROUTE_RANK1 && pre);
-    return two_pass(ch.blocks(), list_pass, false, st, rep, [&](int64_t c, const ChunkLists &w) -> int {
+    const bool embed_list = (embed_defers(a.block) && route != TMFWM_ROUTE_REFERENCE && route != TMFWM_ROUTE_RANK1_REFERENCE) ||
+                            (route == TMFWM_ROUTE_RANK1 && pre);
+    const bool composed = embed_key_composed(a.block, route, a.key_out != nullptr);
+    std::vector<int64_t> blocks = ch.blocks();
+    if (composed) blocks.insert(blocks.end(), blocks.begin(), blocks.begin() + ch.n);  // the map's chunks
+    const bool map_list = composed && route != TMFWM_ROUTE_REFERENCE;
+    return two_pass(blocks, embed_list || map_list, false, st, rep, [&](int64_t cc, const ChunkLists &w) -> int {
+        const int64_t c = cc % ch.n, f0 = ch.first(c), nb = ch.count(c) * ch.per_frame;
+        if (cc >= ch.n) {  // composed: tmfwm_sigma1_map's passes over the chunk (run_keyed)
+            KeyedArgs m = keyed_args(ch.count(c), a.H, a.W, a.frame_stride, a.block, 1.0);
+            m.src = a.src + f0 * a.frame_stride;
+            m.key_out = a.key_out + f0 * a.key_stride;
+            m.key_stride = a.key_stride;
+            m.aligned = dev_aligned(m.src, m.src, a.frame_stride, a.W);
+            wire_lists(m, w);
+            if (route == TMFWM_ROUTE_REFERENCE) TMF_HIP(launch_list_all(m.fb_list, m.fb_count, nb, st));
+            else TMF_HIP(launch_sigma1_map(m, st));
+            TMF_HIP(launch_sigma1_fixup(m, m.fb_list, m.fb_count, nb, st));
+            return 0;
+        }
         EmbedArgs k = a;
-        const int64_t f0 = ch.first(c), nb = ch.count(c) * ch.per_frame;
         k.nframes = ch.count(c);
         k.src = a.src + f0 * a.frame_stride;
         k.dst = a.dst + f0 * a.frame_stride;
         k.wm = a.wm + f0 * a.wm_stride;  // the lists' block ids are relative to the chunk: so is its first tile
+        k.key_out = a.key_out && !composed ? a.key_out + f0 * a.key_stride : nullptr;  // ... and its first key
         wire_lists(k, w);
+        if (!embed_list) k.slow_list = k.slow_shards = nullptr;  // (allocated for the map's chunks)
         if (route == TMFWM_ROUTE_REFERENCE || (route == TMFWM_ROUTE_RANK1_REFERENCE && !pre)) {
             // every block on the dgesdd route; the edges as always
             TMF_HIP(launch_edges(k.src, k.dst, k.nframes, k.H, k.W, k.frame_stride, k.block, st));
@@ -630,22 +663,31 @@ int tmfwm_device_count(void)
     return n;
 }
 
-// 3-byte pixels in and out, one frame stride (tmfwm_embed_route; tmfwm_embed_tiles' 3 -> 3 case):
-// frame f's tile at wm_tile + f * tile_stride (0: one tile for every frame)
+// 3-byte pixels in and out, one frame stride (tmfwm_embed_route; tmfwm_embed_tiles' 3 -> 3 case;
+// tmfwm_embed_key): frame f's tile at wm_tile + f * tile_stride (0: one tile for every frame);
+// with_key: frame f's key to out_key + f * key_stride bytes
 static int embed_rgb(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
                      const uint8_t *wm_tile, int64_t tile_stride, int32_t block, double alpha, uint8_t *out, int32_t mem_kind,
-                     void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+                     void *hip_stream, int32_t route, int64_t *n_lapack_blocks, bool with_key = false, float *out_key = nullptr,
+                     int64_t key_stride = 0)
 {
     if (int rc = begin_call(route, n_lapack_blocks)) return rc;
     if (int rc = check_frames(n_frames, height, width, frame_stride, block)) return rc;
     const int nbh = height / block, nbw = width / block;
     if (int rc = check_tile_stride(tile_stride, (int64_t)nbh * nbw)) return rc;
     if (!std::isfinite(alpha)) return fail(TMFWM_ERR_INVALID, "alpha is not finite");
+    const int64_t kbytes = (int64_t)nbh * nbw * 4;
+    if (with_key && n_frames > 1 && (key_stride % 4 != 0 || key_stride < kbytes))
+        return fail(TMFWM_ERR_INVALID, "key_stride %lld: a multiple of 4 >= (H/block)*(W/block)*4 = %lld", (long long)key_stride,
+                    (long long)kbytes);
     if (int rc = need_device()) return rc;
     if (n_frames == 0 || height == 0 || width == 0) return 0;
+    with_key = with_key && kbytes > 0;  // no block: the colour round trip and no key entry
+    if (n_frames == 1) key_stride = kbytes;
     const int64_t fbytes = (int64_t)height * width * 3;
     const size_t span = span_bytes(n_frames, frame_stride, fbytes), tbytes = (size_t)nbh * nbw;
     const size_t tspan = span_bytes(n_frames, tile_stride, (int64_t)tbytes);  // every frame's tile
+    const size_t kspan = with_key ? (size_t)((n_frames - 1) * key_stride + kbytes) : 0;
     hipStream_t st = pick_stream(hip_stream);
     tmf::EmbedArgs a = tmf::embed_args(n_frames, height, width, frame_stride, block, alpha);
     if (mem_kind == TMFWM_MEM_DEVICE) {
@@ -656,6 +698,15 @@ static int embed_rgb(const uint8_t *rgb, int64_t n_frames, int32_t height, int32
         }
         if (ranges_overlap(rgb, span, out, span)) return fail(TMFWM_ERR_INVALID, "out overlaps rgb (in-place embed is not supported)");
         if (tbytes && ranges_overlap(wm_tile, tspan, out, span)) return fail(TMFWM_ERR_INVALID, "out overlaps wm_tile");
+        if (with_key) {
+            if (int rc = check_device_ptr(out_key, "out_key")) return rc;
+            if (reinterpret_cast<uintptr_t>(out_key) % 4) return fail(TMFWM_ERR_INVALID, "out_key is not 4-byte aligned");
+            if (ranges_overlap(out_key, kspan, rgb, span) || ranges_overlap(out_key, kspan, wm_tile, tspan))
+                return fail(TMFWM_ERR_INVALID, "out_key's output overlaps an input of the call");
+            if (ranges_overlap(out_key, kspan, out, span)) return fail(TMFWM_ERR_INVALID, "out_key's output overlaps out");
+            a.key_out = out_key;
+            a.key_stride = key_stride / 4;
+        }
         a.src = rgb;
         a.dst = out;
         a.wm = wm_tile;
@@ -664,16 +715,23 @@ static int embed_rgb(const uint8_t *rgb, int64_t n_frames, int32_t height, int32
         return tmf::run_embed(a, st, device_report(n_lapack_blocks), route);
     }
     if (mem_kind != TMFWM_MEM_HOST) return fail(TMFWM_ERR_INVALID, "mem_kind %d", mem_kind);
-    if (!rgb || !out || (tbytes && !wm_tile)) return fail(TMFWM_ERR_INVALID, "NULL host pointer");
-    DevBuf din, dout, dwm;
+    if (!rgb || !out || (tbytes && !wm_tile) || (with_key && !out_key)) return fail(TMFWM_ERR_INVALID, "NULL host pointer");
+    if (with_key && reinterpret_cast<uintptr_t>(out_key) % 4) return fail(TMFWM_ERR_INVALID, "out_key is not 4-byte aligned");
+    DevBuf din, dout, dwm, dkey;
     if (int rc = din.alloc(span, st, "input frames")) return rc;
     if (int rc = dout.alloc(span, st, "output frames")) return rc;
+    if (with_key) {  // staged compact
+        if (int rc = dkey.alloc((size_t)(kbytes * n_frames), st, "sigma_1 key maps")) return rc;
+        a.key_out = static_cast<float *>(dkey.p);
+        a.key_stride = kbytes / 4;
+    }
     TMF_HIP(hipMemcpyAsync(din.p, rgb, span, hipMemcpyHostToDevice, st));
     if (int rc = stage_tiles(wm_tile, n_frames, tile_stride, tbytes, st, dwm, &a.wm, &a.wm_stride)) return rc;
     a.src = static_cast<const uint8_t *>(din.p);
     a.dst = static_cast<uint8_t *>(dout.p);
     a.aligned = frame_stride % 4 == 0 && width % 4 == 0;
-    HostCall hc(tmf::count_chunks(n_frames, height, width, block), st, n_lapack_blocks);
+    const int64_t nch = tmf::count_chunks(n_frames, height, width, block);
+    HostCall hc(tmf::embed_key_composed(block, route, with_key) ? 2 * nch : nch, st, n_lapack_blocks);
     if (int rc = tmf::run_embed(a, st, hc.report(), route)) return rc;
     if (frame_stride == fbytes) {
         TMF_HIP(hipMemcpyAsync(out, dout.p, span, hipMemcpyDeviceToHost, st));
@@ -682,7 +740,25 @@ static int embed_rgb(const uint8_t *rgb, int64_t n_frames, int32_t height, int32
             TMF_HIP(hipMemcpyAsync(out + f * frame_stride, static_cast<uint8_t *>(dout.p) + f * frame_stride, (size_t)fbytes,
                                    hipMemcpyDeviceToHost, st));
     }
+    if (with_key) {  // as the frames: one copy, or one per frame past the caller's padding
+        const uint8_t *dk = static_cast<const uint8_t *>(dkey.p);
+        if (key_stride == kbytes) {
+            TMF_HIP(hipMemcpyAsync(out_key, dk, (size_t)(kbytes * n_frames), hipMemcpyDeviceToHost, st));
+        } else {
+            for (int64_t f = 0; f < n_frames; ++f)
+                TMF_HIP(hipMemcpyAsync(reinterpret_cast<uint8_t *>(out_key) + f * key_stride, dk + f * kbytes, (size_t)kbytes,
+                                       hipMemcpyDeviceToHost, st));
+        }
+    }
     return hc.finish();
+}
+
+int tmfwm_embed_key(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
+                    const uint8_t *wm_tiles, int64_t tile_stride, int32_t block, double alpha, uint8_t *out, float *out_key,
+                    int64_t key_stride, int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    return embed_rgb(rgb, n_frames, height, width, frame_stride, wm_tiles, tile_stride, block, alpha, out, mem_kind, hip_stream, route,
+                     n_lapack_blocks, true, out_key, key_stride);
 }
 
 int tmfwm_embed_route(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
@@ -1372,7 +1448,9 @@ enum class RKind {
     Extract,  // in0 = wm_rgb, in1 = orig_rgb, out = out_tile (bytes)
     Map,      // in0 = rgb, no in1, out = out_key (floats)
     Keyed,    // in0 = wm_rgb, in1 = key (floats), out = out_tile (bytes)
+    EmbedKey, // Embed, and out2 = out_key (floats): the frame's second output
 };
+bool embeds(RKind k) { return k == RKind::Embed || k == RKind::EmbedKey; }
 
 // One frame of a ragged call once its descriptor is checked; the descriptor array is not read
 // after that.
@@ -1380,23 +1458,25 @@ struct RFrame {
     const uint8_t *in0, *in1;
     uint8_t *out;
     int32_t H, W;
+    uint8_t *out2 = nullptr;  // RKind::EmbedKey only
     int64_t pixel_bytes() const { return (int64_t)H * W * 3; }
     int64_t tile_bytes(int b) const { return (int64_t)(H / b) * (W / b); }
     // the bytes behind in1 and out
     int64_t in1_bytes(RKind k, int b) const
     {
-        return k == RKind::Embed ? tile_bytes(b) : k == RKind::Extract ? pixel_bytes() : k == RKind::Keyed ? tile_bytes(b) * 4 : 0;
+        return embeds(k) ? tile_bytes(b) : k == RKind::Extract ? pixel_bytes() : k == RKind::Keyed ? tile_bytes(b) * 4 : 0;
     }
     int64_t out_bytes(RKind k, int b) const
     {
-        return k == RKind::Embed ? pixel_bytes() : k == RKind::Map ? tile_bytes(b) * 4 : tile_bytes(b);
+        return embeds(k) ? pixel_bytes() : k == RKind::Map ? tile_bytes(b) * 4 : tile_bytes(b);
     }
+    int64_t out2_bytes(RKind k, int b) const { return k == RKind::EmbedKey ? tile_bytes(b) * 4 : 0; }
     // embed writes every frame that has a pixel (its colour round trip); the others only frames with a block
-    bool has_work(RKind k, int b) const { return pixel_bytes() > 0 && (k == RKind::Embed || tile_bytes(b) > 0); }
+    bool has_work(RKind k, int b) const { return pixel_bytes() > 0 && (embeds(k) || tile_bytes(b) > 0); }
 };
 
-const char *const kRaggedNames[4][3] = {{"rgb", "wm_tile", "out"}, {"wm_rgb", "orig_rgb", "out_tile"}, {"rgb", "", "out_key"},
-                                        {"wm_rgb", "key", "out_tile"}};
+const char *const kRaggedNames[5][3] = {{"rgb", "wm_tile", "out"}, {"wm_rgb", "orig_rgb", "out_tile"}, {"rgb", "", "out_key"},
+                                        {"wm_rgb", "key", "out_tile"}, {"rgb", "wm_tile", "out"}};
 
 // the checks every ragged call makes before it touches the device
 int check_ragged_call(const void *frames, int64_t n, int32_t block, double alpha, RKind kind, int32_t mem_kind, int32_t route,
@@ -1420,12 +1500,14 @@ int check_ragged_frame(int64_t i, const RFrame &f, int32_t block, RKind kind)
     if (f.H == 0 || f.W == 0) return 0;
     if (f.tile_bytes(block) > 0x7FFFFFFFll) return fail(TMFWM_ERR_INVALID, "frame %lld: more than 2^31 - 1 blocks", (long long)i);
     const bool tile = f.tile_bytes(block) > 0;
-    if (kind == RKind::Embed ? (!f.in0 || !f.out || (tile && !f.in1)) : (tile && (!f.in0 || (kind != RKind::Map && !f.in1) || !f.out)))
+    if (embeds(kind) ? (!f.in0 || !f.out || (tile && (!f.in1 || (kind == RKind::EmbedKey && !f.out2))))
+                     : (tile && (!f.in0 || (kind != RKind::Map && !f.in1) || !f.out)))
         return fail(TMFWM_ERR_INVALID, "frame %lld: NULL pointer in the descriptor", (long long)i);
     // the float pieces are read and written as floats
-    const uint8_t *fl = kind == RKind::Keyed ? f.in1 : kind == RKind::Map ? f.out : nullptr;
+    const uint8_t *fl = kind == RKind::Keyed ? f.in1 : kind == RKind::Map ? f.out : kind == RKind::EmbedKey ? f.out2 : nullptr;
     if (tile && reinterpret_cast<uintptr_t>(fl) % 4)
-        return fail(TMFWM_ERR_INVALID, "frame %lld: %s is not 4-byte aligned", (long long)i, kRaggedNames[(int)kind][kind == RKind::Keyed ? 1 : 2]);
+        return fail(TMFWM_ERR_INVALID, "frame %lld: %s is not 4-byte aligned", (long long)i,
+                    kind == RKind::EmbedKey ? "out_key" : kRaggedNames[(int)kind][kind == RKind::Keyed ? 1 : 2]);
     return 0;
 }
 
@@ -1464,15 +1546,18 @@ int check_ragged_device(const std::vector<RFrame> &fr, int32_t block, RKind kind
     };
     for (size_t i = 0; i < fr.size(); ++i) {
         const RFrame &f = fr[i];
-        const int64_t ib = f.in1_bytes(kind, block);
+        const int64_t ib = f.in1_bytes(kind, block), kb = f.out2_bytes(kind, block);
         if (!f.has_work(kind, block)) continue;
         if (int rc = check_device_ptr(f.in0, name[0])) return rc;
         if (ib)
             if (int rc = check_device_ptr(f.in1, name[1])) return rc;
         if (int rc = check_device_ptr(f.out, name[2])) return rc;
+        if (kb)
+            if (int rc = check_device_ptr(f.out2, "out_key")) return rc;
         add(f.in0, f.pixel_bytes(), false, (int64_t)i);
         if (ib) add(f.in1, ib, false, (int64_t)i);
         add(f.out, f.out_bytes(kind, block), true, (int64_t)i);
+        if (kb) add(f.out2, kb, true, (int64_t)i);
     }
     return check_ragged_overlap(spans);
 }
@@ -1548,8 +1633,9 @@ struct RaggedChunk {
 constexpr int64_t kEdgeCap = int64_t(1) << 38;
 
 // the frame table of the frames that have work, with chunk-relative prefixes, and the chunks
+// (RKind::EmbedKey: `keys` receives the table's side table, each entry's key output)
 void plan_ragged(const std::vector<RFrame> &fr, int32_t block, RKind kind, std::vector<tmf::RaggedFrame> &table,
-                 std::vector<RaggedChunk> &chunks)
+                 std::vector<RaggedChunk> &chunks, std::vector<float *> &keys)
 {
     const int bpw = tmf::ragged_strip_blocks(block);
     const int64_t cap = list_cap();
@@ -1565,9 +1651,9 @@ void plan_ragged(const std::vector<RFrame> &fr, int32_t block, RKind kind, std::
         t.nbw = f.W / block;
         t.strips_per_row = (t.nbw + bpw - 1) / bpw;
         // the frame's pixel buffers: two of them, or the single one of the keyed calls
-        t.aligned = tmf::dev_aligned(f.in0, kind == RKind::Embed ? f.out : kind == RKind::Extract ? f.in1 : f.in0, 0, f.W);
+        t.aligned = tmf::dev_aligned(f.in0, embeds(kind) ? f.out : kind == RKind::Extract ? f.in1 : f.in0, 0, f.W);
         const int64_t waves = (int64_t)t.nbh * t.strips_per_row, blocks = (int64_t)t.nbh * t.nbw;
-        const int64_t edge = kind == RKind::Embed ? (int64_t)f.H * f.W - blocks * block * block : 0;
+        const int64_t edge = embeds(kind) ? (int64_t)f.H * f.W - blocks * block * block : 0;
         if (blocks == 0 && edge == 0) continue;
         if (c.n > 0 && (c.blocks + blocks > cap || c.edge + edge > kEdgeCap)) {
             chunks.push_back(c);
@@ -1578,6 +1664,7 @@ void plan_ragged(const std::vector<RFrame> &fr, int32_t block, RKind kind, std::
         t.block0 = (uint32_t)c.blocks;
         t.edge0 = c.edge;
         table.push_back(t);
+        if (kind == RKind::EmbedKey) keys.push_back(reinterpret_cast<float *>(f.out2));
         ++c.n;
         c.waves += waves;
         c.blocks += blocks;
@@ -1590,13 +1677,15 @@ void plan_ragged(const std::vector<RFrame> &fr, int32_t block, RKind kind, std::
 // chunks through two_pass, with the edge pass between a chunk's first pass and its fixup pass and
 // neither of the two for a chunk without a block.
 int run_ragged(int32_t block, double alpha, RKind kind, hipStream_t st, int route, const Report &rep,
-               const std::vector<tmf::RaggedFrame> &table, const std::vector<RaggedChunk> &chunks)
+               const std::vector<tmf::RaggedFrame> &table, const std::vector<RaggedChunk> &chunks, const std::vector<float *> &keys)
 {
     if (chunks.empty()) return 0;
-    const size_t tbytes = table.size() * sizeof(tmf::RaggedFrame);
+    // the frame table and behind it the key side table (RKind::EmbedKey; empty otherwise), one upload
+    const size_t fbytes = table.size() * sizeof(tmf::RaggedFrame), tbytes = fbytes + keys.size() * sizeof(float *);
     TableSlot slot;
     if (int rc = take_table(tbytes, stream_device(st), slot)) return rc;
     std::copy(table.begin(), table.end(), static_cast<tmf::RaggedFrame *>(slot.p));
+    std::copy(keys.begin(), keys.end(), reinterpret_cast<float **>(static_cast<uint8_t *>(slot.p) + fbytes));
     DevBuf dtable;
     int rc = dtable.alloc(tbytes, st, "frame table");
     if (rc == 0 && hipMemcpyAsync(dtable.p, slot.p, tbytes, hipMemcpyHostToDevice, st) != hipSuccess)
@@ -1607,7 +1696,7 @@ int run_ragged(int32_t block, double alpha, RKind kind, hipStream_t st, int rout
     for (const RaggedChunk &k : chunks) blocks.push_back(k.blocks);
     return two_pass(blocks, false, true, st, rep, [&](int64_t c, const ChunkLists &w) -> int {
         const RaggedChunk &k = chunks[(size_t)c];
-        tmf::RaggedArgs r{};
+        tmf::RaggedKeyArgs r{};  // (the other kinds take its RaggedArgs part)
         r.frames = static_cast<const tmf::RaggedFrame *>(dtable.p) + k.first;
         r.nframes = (int32_t)k.n;
         r.block = block;
@@ -1616,17 +1705,20 @@ int run_ragged(int32_t block, double alpha, RKind kind, hipStream_t st, int rout
         r.fb_list = w.fb_list;  // no list pass in a ragged call
         r.fb_count = w.fb_count;
         r.fb_bad = w.fb_bad;
+        if (kind == RKind::EmbedKey) r.keys = reinterpret_cast<float *const *>(static_cast<const uint8_t *>(dtable.p) + fbytes) + k.first;
         if (k.blocks > 0) {
             if (route == TMFWM_ROUTE_REFERENCE) TMF_HIP(tmf::launch_list_all(r.fb_list, r.fb_count, k.blocks, st));
             else
-                TMF_HIP(kind == RKind::Embed     ? tmf::launch_embed_ragged(r, k.waves, st)
+                TMF_HIP(kind == RKind::EmbedKey  ? tmf::launch_embed_key_ragged(r, k.waves, st)
+                        : kind == RKind::Embed   ? tmf::launch_embed_ragged(r, k.waves, st)
                         : kind == RKind::Extract ? tmf::launch_extract_ragged(r, k.waves, st)
                         : kind == RKind::Map     ? tmf::launch_sigma1_map_ragged(r, k.waves, st)
                                                  : tmf::launch_extract_keyed_ragged(r, k.waves, st));
         }
-        if (kind == RKind::Embed) TMF_HIP(tmf::launch_edges_ragged(r, k.edge, st));
+        if (embeds(kind)) TMF_HIP(tmf::launch_edges_ragged(r, k.edge, st));
         if (k.blocks > 0)
-            TMF_HIP(kind == RKind::Embed     ? tmf::launch_embed_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st)
+            TMF_HIP(kind == RKind::EmbedKey  ? tmf::launch_embed_key_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st)
+                    : kind == RKind::Embed   ? tmf::launch_embed_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st)
                     : kind == RKind::Extract ? tmf::launch_extract_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st)
                     : kind == RKind::Map     ? tmf::launch_sigma1_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st)
                                              : tmf::launch_extract_keyed_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st));
@@ -1646,22 +1738,25 @@ int ragged_call(std::vector<RFrame> &fr, int32_t block, double alpha, RKind kind
     hipStream_t st = pick_stream(hip_stream);
     std::vector<tmf::RaggedFrame> table;
     std::vector<RaggedChunk> chunks;
+    std::vector<float *> keys;
     if (mem_kind == TMFWM_MEM_DEVICE) {
         if (int rc = check_ragged_device(fr, block, kind)) return rc;
-        plan_ragged(fr, block, kind, table, chunks);
-        return run_ragged(block, alpha, kind, st, route, device_report(n_lapack), table, chunks);
+        plan_ragged(fr, block, kind, table, chunks, keys);
+        return run_ragged(block, alpha, kind, st, route, device_report(n_lapack), table, chunks, keys);
     }
     // host memory: every buffer of the call in one device allocation (16-byte aligned pieces),
     // results copied back, one synchronisation
     std::vector<RFrame> dv(fr);
     size_t total = 0;
-    std::vector<size_t> off(fr.size() * 3);
+    std::vector<size_t> off(fr.size() * 3), off2(fr.size());
     for (size_t i = 0; i < fr.size(); ++i) {
         const size_t sz[3] = {(size_t)fr[i].pixel_bytes(), (size_t)fr[i].in1_bytes(kind, block), (size_t)fr[i].out_bytes(kind, block)};
         for (int k = 0; k < 3; ++k) {
             off[3 * i + k] = total;
             total += round16(sz[k]);
         }
+        off2[i] = total;
+        total += round16((size_t)fr[i].out2_bytes(kind, block));
     }
     DevBuf stage;
     if (int rc = stage.alloc(total, st, "ragged frames")) return rc;
@@ -1672,15 +1767,18 @@ int ragged_call(std::vector<RFrame> &fr, int32_t block, double alpha, RKind kind
         dv[i].in0 = base + off[3 * i];
         dv[i].in1 = ib ? base + off[3 * i + 1] : nullptr;
         dv[i].out = base + off[3 * i + 2];
+        dv[i].out2 = fr[i].out2_bytes(kind, block) ? base + off2[i] : nullptr;
         TMF_HIP(hipMemcpyAsync(base + off[3 * i], fr[i].in0, (size_t)fr[i].pixel_bytes(), hipMemcpyHostToDevice, st));
         if (ib) TMF_HIP(hipMemcpyAsync(base + off[3 * i + 1], fr[i].in1, ib, hipMemcpyHostToDevice, st));
     }
-    plan_ragged(dv, block, kind, table, chunks);
+    plan_ragged(dv, block, kind, table, chunks, keys);
     HostCall hc((int64_t)chunks.size(), st, n_lapack);
-    if (int rc = run_ragged(block, alpha, kind, st, route, hc.report(), table, chunks)) return rc;
+    if (int rc = run_ragged(block, alpha, kind, st, route, hc.report(), table, chunks, keys)) return rc;
     for (size_t i = 0; i < fr.size(); ++i) {
         if (!fr[i].has_work(kind, block)) continue;
         TMF_HIP(hipMemcpyAsync(fr[i].out, dv[i].out, (size_t)fr[i].out_bytes(kind, block), hipMemcpyDeviceToHost, st));
+        if (const size_t kb = (size_t)fr[i].out2_bytes(kind, block))
+            TMF_HIP(hipMemcpyAsync(fr[i].out2, dv[i].out2, kb, hipMemcpyDeviceToHost, st));
     }
     return hc.finish();
 }
@@ -1798,6 +1896,17 @@ int tmfwm_embed_ragged(const tmfwm_embed_frame *frames, int64_t n_frames, int32_
     std::vector<RFrame> fr((size_t)n_frames);  // the library's copy: the caller's array is not read again
     for (int64_t i = 0; i < n_frames; ++i) fr[(size_t)i] = {frames[i].rgb, frames[i].wm_tile, frames[i].out, frames[i].height, frames[i].width};
     return ragged_call(fr, block, alpha, RKind::Embed, mem_kind, hip_stream, route, n_lapack_blocks);
+}
+
+int tmfwm_embed_key_ragged(const tmfwm_embed_key_frame *frames, int64_t n_frames, int32_t block, double alpha, int32_t mem_kind,
+                           void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    if (int rc = check_ragged_call(frames, n_frames, block, alpha, RKind::EmbedKey, mem_kind, route, n_lapack_blocks)) return rc;
+    std::vector<RFrame> fr((size_t)n_frames);
+    for (int64_t i = 0; i < n_frames; ++i)
+        fr[(size_t)i] = {frames[i].rgb, frames[i].wm_tile, frames[i].out, frames[i].height, frames[i].width,
+                         reinterpret_cast<uint8_t *>(frames[i].out_key)};
+    return ragged_call(fr, block, alpha, RKind::EmbedKey, mem_kind, hip_stream, route, n_lapack_blocks);
 }
 
 int tmfwm_extract_ragged(const tmfwm_extract_frame *frames, int64_t n_frames, int32_t block, double alpha, int32_t mem_kind,

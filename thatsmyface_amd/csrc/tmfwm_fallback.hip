@@ -10,6 +10,7 @@ namespace tmf {
 
 hipError_t launch_embed_fixup(const EmbedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st)
 {
+    if (a.key_out) return for_block(a.block, [&](auto b) { return embed_key_fixup_b<b()>(a, list, count, max_entries, st); });
     return for_block(a.block, [&](auto b) { return embed_fixup_b<b()>(a, list, count, max_entries, st); });
 }
 

@@ -128,7 +128,9 @@ TMF_DEVI void block_of(uint32_t id, uint32_t per_frame, int nbw, int64_t &fr, in
 
 // One listed block end to end on the dgesdd route, by G lanes (gl = this lane's index among
 // them) under lane policy Par: a group of a GroupPar wave, or a whole wave (WavePar, G = 64).
-template <int B, class Par, int G>
+// KEY: the route's S[0] before the blend -- the block's key entry -- goes to
+// a.key_out: over what the strip pass stored, or where it stored nothing.
+template <int B, class Par, int G, bool KEY = false>
 TMF_DEVI void embed_fix_block(const EmbedArgs &a, uint32_t id, FixLds<B> &f, int gl)
 {
     const uint32_t per_frame = (uint32_t)a.nbh * (uint32_t)a.nbw;
@@ -146,6 +148,9 @@ TMF_DEVI void embed_fix_block(const EmbedArgs &a, uint32_t id, FixLds<B> &f, int
     const double *U64 = f.ws + B * B, *VT64 = f.ws + 2 * B * B;
     float *M = f.M();
     const double w = (double)a.wm[fr * a.wm_stride + (int64_t)bi * a.nbw + bj];
+    if constexpr (KEY) {
+        if (gl == 0) a.key_out[fr * a.key_stride + (int64_t)bi * a.nbw + bj] = S[0];
+    }
     const float s0 = (float)((double)S[0] + a.alpha * (w / 255.0));
     for (int e = gl; e < B * B; e += G) {
         const int i = e / B, j = e % B;

@@ -16,6 +16,16 @@ __global__ __launch_bounds__(64) void embed_fixup_kernel(EmbedArgs a, const uint
     });
 }
 
+// embed's key variant (a.key_out set): each listed block's S[0] into its key entry as well
+template <int B>
+__global__ __launch_bounds__(64) void embed_key_fixup_kernel(EmbedArgs a, const uint32_t *__restrict__ list,
+                                                             const uint32_t *__restrict__ count)
+{
+    fixup_walk<B, FixLds<B>>(list, count, [&](auto par, uint32_t id, FixLds<B> &f, int gl) {
+        embed_fix_block<B, typename decltype(par)::Par, decltype(par)::G, true>(a, id, f, gl);
+    });
+}
+
 template <int B>
 __global__ __launch_bounds__(64) void extract_fixup_kernel(ExtractArgs a, const uint32_t *__restrict__ list,
                                                            const uint32_t *__restrict__ count)
@@ -32,12 +42,19 @@ hipError_t embed_fixup_b(const EmbedArgs &a, const uint32_t *list, const uint32_
 }
 
 template <int B>
+hipError_t embed_key_fixup_b(const EmbedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st)
+{
+    return launch_fixup<B>(embed_key_fixup_kernel<B>, a, list, count, max_entries, st);
+}
+
+template <int B>
 hipError_t extract_fixup_b(const ExtractArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st)
 {
     return launch_fixup<B>(extract_fixup_kernel<B>, a, list, count, max_entries, st);
 }
 
 template hipError_t embed_fixup_b<TMF_B>(const EmbedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
+template hipError_t embed_key_fixup_b<TMF_B>(const EmbedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
 template hipError_t extract_fixup_b<TMF_B>(const ExtractArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
 
 }  // namespace tmf

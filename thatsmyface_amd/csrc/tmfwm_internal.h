@@ -44,6 +44,11 @@ struct EmbedArgs {
     uint32_t *slow_list;
     uint32_t *slow_count;
     uint32_t *slow_shards;
+    // the key variants of the embed kernels (tmfwm_embed_key.h) store f32(sigma_1) of
+    // every block of `src` here, as sigma1_map does: nframes x (nbh x nbw) f32, key_stride floats
+    // apart.  Null / 0 in every other call (the plain kernels never read them).
+    float *key_out;
+    int64_t key_stride;
 };
 
 struct ExtractArgs {
@@ -150,7 +155,9 @@ inline hipError_t launch_strips(Args a, int bpw, void (*strip)(Args), void (*lis
     return hipGetLastError();
 }
 
-hipError_t launch_embed(const EmbedArgs &a, hipStream_t st);
+hipError_t launch_embed(const EmbedArgs &a, hipStream_t st);  // a.key_out set: the key variants (tmfwm_embed_key.hip)
+hipError_t launch_embed_key_strips(const EmbedArgs &a, hipStream_t st);
+bool embed_key_fused(int block);  // the key comes out of the embed passes at this size (tmfwm_embed_key.h)
 hipError_t launch_embed_rank1(EmbedArgs a, hipStream_t st);  // TMFWM_ROUTE_RANK1 (tmfwm_rank1.hip)
 bool rank1_block(int block);  // the block sizes TMFWM_ROUTE_RANK1 has a pre-pass for
 bool embed_defers(int block);  // the strip pass of embed_kernel<block> can leave blocks to a list pass
@@ -167,6 +174,10 @@ hipError_t launch_extract_fixup(const ExtractArgs &a, const uint32_t *list, cons
 // size's own translation unit (tmfwm_fixup.hip, tmfwm_keyed_fixup.hip), which alone sees the kernels
 template <int B>
 hipError_t embed_fixup_b(const EmbedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
+template <int B>
+hipError_t embed_key_fixup_b(const EmbedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
+template <int B>
+hipError_t embed_key_strips_b(const EmbedArgs &a, hipStream_t st);  // tmfwm_embed_key.hip
 template <int B>
 hipError_t extract_fixup_b(const ExtractArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
 template <int B>

@@ -246,11 +246,22 @@ bool embed_defers(int block)
     return block_value(block, false, [](auto b) { return kDeferMax<b()> > 0; });
 }
 
+bool embed_key_fused(int block)
+{
+    return block_value(block, false, [](auto b) { return kEmbedKeyFused<b()>; });
+}
+
+// the key variants of the strip and list passes, one TU per block size (tmfwm_embed_key.hip)
+hipError_t launch_embed_key_strips(const EmbedArgs &a, hipStream_t st)
+{
+    return for_block(a.block, [&](auto b) { return embed_key_strips_b<b()>(a, st); });
+}
+
 hipError_t launch_embed(const EmbedArgs &a, hipStream_t st)
 {
     if (a.nbh > 0 && a.nbw > 0) {
         // the list pass takes the blocks the first pass left unfinished (ids relative to a.src)
-        const hipError_t e = for_block(a.block, [&](auto b) {
+        const hipError_t e = a.key_out ? launch_embed_key_strips(a, st) : for_block(a.block, [&](auto b) {
             constexpr int B = b();
             void (*list)(EmbedArgs) = nullptr;
             if constexpr (kDeferMax<B> > 0) list = embed_kernel<B, true>;

@@ -40,6 +40,13 @@ struct RaggedArgs {
     uint32_t *fb_bad;
 };
 
+// embed with key (tmfwm_embed_key.h): frame i's nbh x nbw f32 key output at keys[i] (device
+// memory, indexed as `frames`; 4-byte aligned) -- a side table and an argument struct of this call
+// kind's own, so that the frame table keeps its 64-byte entry and the other kinds their arguments
+struct RaggedKeyArgs : RaggedArgs {
+    float *const *keys;
+};
+
 // blocks per strip wave at this block size (Geo<b>::BPW): the host needs it for strips_per_row
 int ragged_strip_blocks(int block);
 // strip pass of a chunk: `waves` = the chunk's strip waves (> 0), one workgroup each
@@ -47,6 +54,10 @@ hipError_t launch_embed_ragged(const RaggedArgs &r, int64_t waves, hipStream_t s
 hipError_t launch_extract_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st);
 hipError_t launch_sigma1_map_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st);
 hipError_t launch_extract_keyed_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st);
+// embed's key variants: the strip pass and the dgesdd route, each storing its blocks' key entries
+hipError_t launch_embed_key_ragged(const RaggedKeyArgs &r, int64_t waves, hipStream_t st);
+hipError_t launch_embed_key_ragged_fixup(const RaggedKeyArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
+                                         hipStream_t st);
 // colour round trip of the chunk's `pixels` edge pixels (embed)
 hipError_t launch_edges_ragged(const RaggedArgs &r, int64_t pixels, hipStream_t st);
 // the dgesdd route over the chunk's list (ids as above), max_entries bounds the list
@@ -62,6 +73,10 @@ hipError_t launch_extract_keyed_ragged_fixup(const RaggedArgs &r, const uint32_t
 // translation units (tmfwm_ragged_strip.hip, tmfwm_ragged_fixup.hip), which alone see the kernels
 template <int B>
 hipError_t embed_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st);
+template <int B>
+hipError_t embed_key_ragged_b(const RaggedKeyArgs &r, unsigned waves, hipStream_t st);
+template <int B>
+hipError_t embed_key_ragged_fixup_b(const RaggedKeyArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
 template <int B>
 hipError_t extract_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st);
 template <int B>
@@ -85,6 +100,9 @@ hipError_t extract_keyed_ragged_fixup_b(const RaggedArgs &r, const uint32_t *lis
 #define TMF_CONST_AS __attribute__((address_space(4)))
 using RaggedFrameK = const TMF_CONST_AS RaggedFrame;
 __device__ __forceinline__ RaggedFrameK *ragged_const(const RaggedFrame *p) { return (RaggedFrameK *)p; }
+// the key side table the same way (RaggedKeyArgs::keys)
+using RaggedKeyK = float *const TMF_CONST_AS;
+__device__ __forceinline__ RaggedKeyK *ragged_key_const(float *const *p) { return (RaggedKeyK *)p; }
 
 // the frame that owns flat index x: the last i in [0, n) with prefix(i) <= x (frames with
 // nothing to do share their successor's prefix and are never found)
@@ -125,6 +143,8 @@ __device__ __forceinline__ EmbedArgs ragged_embed_view(const RaggedArgs &r, F *f
     a.slow_list = nullptr;  // no list pass: the strip pass runs every block to the end
     a.slow_count = nullptr;
     a.slow_shards = nullptr;
+    a.key_out = nullptr;    // the key variants set it from RaggedKeyArgs::keys
+    a.key_stride = 0;
     return a;
 }
 

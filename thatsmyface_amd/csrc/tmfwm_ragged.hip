@@ -19,6 +19,18 @@ hipError_t launch_embed_ragged(const RaggedArgs &r, int64_t waves, hipStream_t s
     return for_block(r.block, [&](auto b) { return embed_ragged_b<b()>(r, (unsigned)waves, st); });
 }
 
+hipError_t launch_embed_key_ragged(const RaggedKeyArgs &r, int64_t waves, hipStream_t st)
+{
+    if (waves <= 0 || waves > kGridMax) return hipErrorInvalidValue;
+    return for_block(r.block, [&](auto b) { return embed_key_ragged_b<b()>(r, (unsigned)waves, st); });
+}
+
+hipError_t launch_embed_key_ragged_fixup(const RaggedKeyArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
+                                         hipStream_t st)
+{
+    return for_block(r.block, [&](auto b) { return embed_key_ragged_fixup_b<b()>(r, list, count, max_entries, st); });
+}
+
 hipError_t launch_extract_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st)
 {
     if (waves <= 0 || waves > kGridMax) return hipErrorInvalidValue;

@@ -27,6 +27,16 @@ TMF_DEVI void embed_ragged_fix(const RaggedArgs &r, uint32_t id, FixLds<B> &f, i
     embed_fix_block<B, Par, G>(a, id - fr->block0, f, gl);
 }
 
+// embed's key variant: the frame's key pointer from the call's side table
+template <int B, class Par, int G>
+TMF_DEVI void embed_key_ragged_fix(const RaggedKeyArgs &r, uint32_t id, FixLds<B> &f, int gl)
+{
+    const RaggedFrame *fr = ragged_block_frame(r, id);
+    EmbedArgs a = ragged_embed_view(r, fr);
+    a.key_out = r.keys[fr - r.frames];
+    embed_fix_block<B, Par, G, true>(a, id - fr->block0, f, gl);
+}
+
 template <int B, class Par, int G>
 TMF_DEVI void extract_ragged_fix(const RaggedArgs &r, uint32_t id, FixLdsS<B> &f, int gl)
 {
@@ -41,6 +51,15 @@ __global__ __launch_bounds__(64) void embed_ragged_fixup_kernel(RaggedArgs r, co
 {
     fixup_walk<B, FixLds<B>>(list, count, [&](auto par, uint32_t id, FixLds<B> &f, int gl) {
         embed_ragged_fix<B, typename decltype(par)::Par, decltype(par)::G>(r, id, f, gl);
+    });
+}
+
+template <int B>
+__global__ __launch_bounds__(64) void embed_key_ragged_fixup_kernel(RaggedKeyArgs r, const uint32_t *__restrict__ list,
+                                                                    const uint32_t *__restrict__ count)
+{
+    fixup_walk<B, FixLds<B>>(list, count, [&](auto par, uint32_t id, FixLds<B> &f, int gl) {
+        embed_key_ragged_fix<B, typename decltype(par)::Par, decltype(par)::G>(r, id, f, gl);
     });
 }
 
@@ -103,12 +122,19 @@ hipError_t embed_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const
 }
 
 template <int B>
+hipError_t embed_key_ragged_fixup_b(const RaggedKeyArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st)
+{
+    return launch_fixup<B>(embed_key_ragged_fixup_kernel<B>, r, list, count, max_entries, st);
+}
+
+template <int B>
 hipError_t extract_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st)
 {
     return launch_fixup<B>(extract_ragged_fixup_kernel<B>, r, list, count, max_entries, st);
 }
 
 template hipError_t embed_ragged_fixup_b<TMF_B>(const RaggedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
+template hipError_t embed_key_ragged_fixup_b<TMF_B>(const RaggedKeyArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
 template hipError_t extract_ragged_fixup_b<TMF_B>(const RaggedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
 template hipError_t sigma1_ragged_fixup_b<TMF_B>(const RaggedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
 template hipError_t extract_keyed_ragged_fixup_b<TMF_B>(const RaggedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);

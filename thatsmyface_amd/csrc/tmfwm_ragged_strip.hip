@@ -57,6 +57,22 @@ __global__ __launch_bounds__(64, kEmbedWaves<B>) void embed_ragged_kernel(Ragged
     embed_blocks<B, false>(a, pos, id, lds, lds2);
 }
 
+// embed's key variant (tmfwm_embed_key.h): the frame's key pointer from the call's side table
+// (r.keys, indexed as r.frames: the 64-byte table entry has no room for a second output)
+template <int B>
+__global__ __launch_bounds__(64, kEmbedWaves<B>) void embed_key_ragged_kernel(RaggedKeyArgs r)
+{
+    constexpr int BPW = Geo<B>::BPW, TS = kEmbedTS<B>;
+    __shared__ __attribute__((aligned(16))) float lds_all[BPW * TS + kHiPad<B> + kLds2Floats<B>];  // as embed_kernel
+    float *lds = lds_all, *lds2 = lds_all + BPW * TS + kHiPad<B>;
+    RaggedFrameK *f = ragged_wave_frame(r);
+    EmbedArgs a = ragged_embed_view(r, f);
+    a.key_out = ragged_key_const(r.keys)[f - ragged_const(r.frames)];
+    uint32_t id;
+    const StripPos pos = ragged_strip_pos<B>(f, id);
+    embed_blocks<B, false, true>(a, pos, id, lds, lds2);
+}
+
 template <int B>
 __global__ __launch_bounds__(64, (B > 8 ? 2 : kExtract8Waves)) void extract_ragged_kernel(RaggedArgs r)
 {
@@ -86,6 +102,13 @@ hipError_t embed_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st)
 }
 
 template <int B>
+hipError_t embed_key_ragged_b(const RaggedKeyArgs &r, unsigned waves, hipStream_t st)
+{
+    hipLaunchKernelGGL((embed_key_ragged_kernel<B>), dim3(waves), dim3(64), 0, st, r);
+    return hipGetLastError();
+}
+
+template <int B>
 hipError_t extract_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st)
 {
     hipLaunchKernelGGL((extract_ragged_kernel<B>), dim3(waves), dim3(64), 0, st, r);
@@ -93,6 +116,7 @@ hipError_t extract_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st)
 }
 
 template hipError_t embed_ragged_b<TMF_B>(const RaggedArgs &, unsigned, hipStream_t);
+template hipError_t embed_key_ragged_b<TMF_B>(const RaggedKeyArgs &, unsigned, hipStream_t);
 template hipError_t extract_ragged_b<TMF_B>(const RaggedArgs &, unsigned, hipStream_t);
 #endif
 

@@ -4,6 +4,7 @@ from ..watermarking import (  # noqa: F401
     apply_dct_to_block,
     apply_idct_to_block,
     embed_watermark,
+    embed_watermark_with_key,
     extract_watermark,
     extract_watermark_keyed,
     extraction_key,

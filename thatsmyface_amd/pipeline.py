@@ -40,10 +40,13 @@ from .constants import ALPHA, BLOCK_SIZE, SVD_ROUTE
 
 @dataclass
 class Embedded:
-    """One pipeline result: the watermarked RGB pixels and their PNG encoding."""
+    """One pipeline result: the watermarked RGB pixels and their PNG encoding; with
+    ``embed_images(..., return_keys=True)`` also the extraction key of the original image
+    (``watermarking.extraction_key``'s float32 array), else None."""
 
     pixels: np.ndarray
     png: bytes
+    key: np.ndarray | None = None
 
     def image(self) -> Image.Image:
         return Image.fromarray(self.pixels, "RGB")
@@ -54,12 +57,12 @@ def _decode(src) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(img.convert("RGB"), dtype=np.uint8))
 
 
-def _encode(pixels: np.ndarray, wait: Callable[[], None] | None) -> Embedded:
+def _encode(pixels: np.ndarray, wait: Callable[[], None] | None, key: np.ndarray | None = None) -> Embedded:
     if wait is not None:
         wait()
     buf = io.BytesIO()
     Image.fromarray(pixels, "RGB").save(buf, format="PNG")  # embed_watermark_page.py:533-535
-    return Embedded(pixels, buf.getvalue())
+    return Embedded(pixels, buf.getvalue(), key)
 
 
 class GpuStage:
@@ -68,9 +71,12 @@ class GpuStage:
     Returns (pixels, wait) where ``wait()`` blocks until the D2H copy landed.  The
     tile for an image size is prepared on the device once and reused.  ``watermark_data``
     may be a list or tuple of watermarks, one per image: the stage is then called as
-    ``stage(rgb, i)`` and keeps its per-size tile cache per watermark."""
+    ``stage(rgb, i)`` and keeps its per-size tile cache per watermark.  With ``return_keys`` the
+    embed is ``embed_with_key`` and the stage returns (pixels, wait, key), the key copied back
+    with the pixels."""
 
-    def __init__(self, watermark_data, block: int, alpha: float, preserve_ratio: bool, device=None, route: str = SVD_ROUTE):
+    def __init__(self, watermark_data, block: int, alpha: float, preserve_ratio: bool, device=None, route: str = SVD_ROUTE,
+                 return_keys: bool = False):
         import torch
 
         from . import batch
@@ -78,6 +84,7 @@ class GpuStage:
         self.torch, self.batch = torch, batch
         self.block, self.alpha, self.preserve_ratio = int(block), float(alpha), bool(preserve_ratio)
         self.route = route  # the drop-in's SVD route (constants.SVD_ROUTE, custom_settings["svd_route"])
+        self.return_keys = bool(return_keys)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.per_image = isinstance(watermark_data, (list, tuple))
         self.wm_grey = []  # one grey watermark on the device per watermark
@@ -104,19 +111,27 @@ class GpuStage:
         host_in = torch.empty((1, h, w, 3), dtype=torch.uint8, pin_memory=True)
         host_in.numpy()[0] = rgb
         host_out = torch.empty((1, h, w, 3), dtype=torch.uint8, pin_memory=True)
+        host_key = torch.empty((1, nbh, nbw), dtype=torch.float32, pin_memory=True) if self.return_keys else None
         tile = self._tile(nbh, nbw, index)
         with torch.cuda.stream(self.stream):
             dev_in = host_in.to(self.device, non_blocking=True)
-            dev_out = self.batch.embed_batch(dev_in, tile, self.block, self.alpha, stream=self.stream, route=self.route)
+            dev_key = None
+            if self.return_keys:
+                dev_out, dev_key = self.batch.embed_with_key(dev_in, tile, self.block, self.alpha, stream=self.stream, route=self.route)
+                host_key.copy_(dev_key, non_blocking=True)
+            else:
+                dev_out = self.batch.embed_batch(dev_in, tile, self.block, self.alpha, stream=self.stream, route=self.route)
             host_out.copy_(dev_out, non_blocking=True)
             done = torch.cuda.Event()
             done.record(self.stream)
         # keep the device buffers alive until the copy has landed
-        keep = (dev_in, dev_out, host_in)
+        keep = (dev_in, dev_out, dev_key, host_in)
 
         def wait(_e=done, _k=keep):
             _e.synchronize()
 
+        if self.return_keys:
+            return host_out.numpy()[0], wait, host_key.numpy()[0]
         return host_out.numpy()[0], wait
 
 
@@ -128,7 +143,8 @@ class RaggedGpuStage(GpuStage):
 
     Called as ``stage(rgbs, indices)`` with the group's pixel arrays and their positions in the
     input (the watermark of image ``i`` is watermark ``i`` when there is one per image); returns
-    one ``(pixels, wait)`` per image, in the group's order."""
+    one ``(pixels, wait)`` per image, in the group's order -- with ``return_keys``, by one
+    ``embed_with_key_ragged``, one ``(pixels, wait, key)`` per image."""
 
     def _group_tiles(self, keys):
         """The tiles of a group's (watermark, nbh, nbw) keys: those the cache does not hold, each
@@ -146,7 +162,7 @@ class RaggedGpuStage(GpuStage):
 
     def __call__(self, rgbs, indices):
         torch = self.torch
-        keys, host_in, host_out = [], [], []
+        keys, host_in, host_out, host_key = [], [], [], []
         for rgb, index in zip(rgbs, indices):
             h, w = rgb.shape[:2]
             nbh, nbw = h // self.block, w // self.block
@@ -157,19 +173,28 @@ class RaggedGpuStage(GpuStage):
             hi.numpy()[...] = rgb
             host_in.append(hi)
             host_out.append(torch.empty((h, w, 3), dtype=torch.uint8, pin_memory=True))
+            if self.return_keys:
+                host_key.append(torch.empty((nbh, nbw), dtype=torch.float32, pin_memory=True))
         with torch.cuda.stream(self.stream):
             tiles = self._group_tiles(keys)
             dev_in = [h.to(self.device, non_blocking=True) for h in host_in]
-            dev_out = self.batch.embed_ragged(dev_in, tiles, self.block, self.alpha, stream=self.stream, route=self.route)
-            for ho, do in zip(host_out, dev_out):
+            dev_key = []
+            if self.return_keys:
+                dev_out, dev_key = self.batch.embed_with_key_ragged(dev_in, tiles, self.block, self.alpha, stream=self.stream,
+                                                                    route=self.route)
+            else:
+                dev_out = self.batch.embed_ragged(dev_in, tiles, self.block, self.alpha, stream=self.stream, route=self.route)
+            for ho, do in zip(host_out + host_key, list(dev_out) + list(dev_key)):
                 ho.copy_(do, non_blocking=True)
             done = torch.cuda.Event()
             done.record(self.stream)
-        keep = (dev_in, dev_out, host_in, tiles)  # alive until the copies have landed
+        keep = (dev_in, dev_out, dev_key, host_in, tiles)  # alive until the copies have landed
 
         def wait(_e=done, _k=keep):
             _e.synchronize()
 
+        if self.return_keys:
+            return [(ho.numpy(), wait, hk.numpy()) for ho, hk in zip(host_out, host_key)]
         return [(ho.numpy(), wait) for ho in host_out]
 
 
@@ -309,7 +334,7 @@ def extract_images(images: Iterable, keys: Sequence, custom_settings: dict | Non
 
 def embed_images(images: Iterable, watermark_data, preserve_ratio: bool = True, custom_settings: dict | None = None,
                  workers: int | None = None, device_stage: Callable | None = None,
-                 batch_images: int | None = None) -> list[Embedded]:
+                 batch_images: int | None = None, return_keys: bool = False) -> list[Embedded]:
     """Embed ``watermark_data`` (PNG bytes or PIL image) into every image (bytes, file
     object or PIL image) -- embed_watermark_page.py:492-558 without the per-image
     serialisation.  Returns, in input order, the watermarked pixels and PNG bytes.
@@ -323,7 +348,13 @@ def embed_images(images: Iterable, watermark_data, preserve_ratio: bool = True, 
     sizes, and embed each group with one ragged launch set (``RaggedGpuStage``; a custom
     ``device_stage`` is then called as ``stage(rgbs, indices)`` and returns one
     ``(pixels, wait)`` per image).  Order, pixels and PNG bytes are those of the per-image path,
-    which ``None`` keeps."""
+    which ``None`` keeps.
+
+    ``return_keys=True`` is the enrolment side of keyed extraction: every ``Embedded`` also carries
+    ``key``, bit for bit ``watermarking.extraction_key(image, custom_settings)`` of the original
+    image, out of the same device call as the pixels (``embed_with_key`` /
+    ``embed_with_key_ragged``) -- what ``extract_images`` takes with the watermarked images.  A
+    custom ``device_stage`` then returns ``(pixels, wait, key)`` per image."""
     settings = custom_settings or {}
     block = int(settings.get("block_size", BLOCK_SIZE))
     alpha = float(settings.get("alpha", ALPHA))
@@ -335,7 +366,15 @@ def embed_images(images: Iterable, watermark_data, preserve_ratio: bool = True, 
     if batch_images is not None and int(batch_images) < 1:
         raise ValueError(f"batch_images must be >= 1 or None, got {batch_images!r}")
     stage = device_stage or (GpuStage if batch_images is None else RaggedGpuStage)(watermark_data, block, alpha, preserve_ratio,
-                                                                                 route=route)
+                                                                                 route=route, **({"return_keys": True} if return_keys else {}))
+    arity = 3 if return_keys else 2
+
+    def checked(result):
+        if len(result) != arity:
+            raise ValueError(f"the device stage returned {len(result)} values per image, {arity} expected"
+                             + (" (pixels, wait, key)" if return_keys else ""))
+        return result
+
     n_workers = workers or min(16, max(2, (len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 4)))
     with ThreadPoolExecutor(n_workers, thread_name_prefix="tmf-io") as pool:
         decoded: list[Future] = [pool.submit(_decode, s) for s in sources]
@@ -346,9 +385,8 @@ def embed_images(images: Iterable, watermark_data, preserve_ratio: bool = True, 
                 results = stage([decoded[i].result() for i in indices], indices)
                 if len(results) != len(indices):
                     raise ValueError(f"the device stage returned {len(results)} results for {len(indices)} images")
-                encoded.extend(pool.submit(_encode, pixels, wait) for pixels, wait in results)
+                encoded.extend(pool.submit(_encode, *checked(r)) for r in results)
             return [f.result() for f in encoded]
         for i, fut in enumerate(decoded):  # the device stage runs in order on this thread
-            pixels, wait = stage(fut.result(), i) if per_image else stage(fut.result())
-            encoded.append(pool.submit(_encode, pixels, wait))
+            encoded.append(pool.submit(_encode, *checked(stage(fut.result(), i) if per_image else stage(fut.result()))))
         return [f.result() for f in encoded]

@@ -43,6 +43,7 @@ __all__ = [
     "extract_watermark",
     "extraction_key",
     "extract_watermark_keyed",
+    "embed_watermark_with_key",
 ]
 
 
@@ -426,6 +427,27 @@ def extraction_key(original_image, custom_settings=None) -> np.ndarray:
         "extraction_key",
     )
     return key
+
+
+def embed_watermark_with_key(image, watermark_data, preserve_ratio=False, custom_settings=None):
+    """embed_watermark and extraction_key(image) in one call and one upload (tmfwm_embed_key):
+    (the watermarked RGB image, the float32 (H//b, W//b) key of `image`).  The image is
+    embed_watermark's pixel for pixel, the key extraction_key's bit for bit: what
+    extract_watermark_keyed takes with the watermarked image.  3-byte pixels on both sides."""
+    block_size, alpha = _block_size(custom_settings)
+    rgb = np.ascontiguousarray(np.asarray(_rgb_image(image), dtype=np.uint8))
+    height, width = rgb.shape[:2]
+    nbh, nbw = height // block_size, width // block_size
+    tile = _tile_for(watermark_data, nbh, nbw, preserve_ratio)
+    out = np.empty_like(rgb)
+    key = np.empty((nbh, nbw), np.float32)
+    L = _lib.load()
+    _lib.check(
+        L.tmfwm_embed_key(_ptr(rgb), 1, height, width, rgb.size, _ptr(tile), 0, block_size, float(alpha), _ptr(out), _ptr(key), 0,
+                          _lib.MEM_HOST, None, _route(custom_settings), None),
+        "embed_watermark_with_key",
+    )
+    return Image.fromarray(out), key
 
 
 def extract_watermark_keyed(watermarked_image, key, custom_settings=None):

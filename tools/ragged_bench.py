@@ -16,12 +16,16 @@ single-frame extract_keyed calls; extract_keyed_ragged against extract_ragged wi
 (the pair path; its time is reported as "base"); sigma1_map_ragged against the loop of 64
 single-frame sigma1_map calls.
 
+Workload E (enrolment): workload A's frames and tiles.  embed_with_key_ragged against
+embed_ragged followed by sigma1_map_ragged (the two-pass way to the same outputs and keys; its
+time is reported as "base"), and against embed_ragged alone (what the key costs).
+
 Both arms of a comparison run alternately in one process, each timing a window of `inner` calls
 that ends in a device synchronise.  Every ratio comes with the A/A spread of its own run: the
 medians of the even and of the odd rounds of the same arm, as a ratio.  The arms' outputs are
 compared byte for byte before anything is timed.
 
-usage: python tools/ragged_bench.py [--workload a|b|k|ab|abk] [--rounds R] [--frames-b N]
+usage: python tools/ragged_bench.py [--workload a|b|k|e|ab|abk] [--rounds R] [--frames-b N]
 """
 import argparse
 import json
@@ -140,6 +144,37 @@ def workload_k(rounds, dev):
                     {"what": "64 images key maps: sigma1_map_ragged vs loop of single-frame sigma1_map", **extra})]
 
 
+def workload_e(rounds, dev):
+    b, alpha, n = 8, 0.1, 64
+    picks, frames, tiles = frames_a(dev, b, n)
+    state = {}
+
+    def two_pass():
+        state["two_pass"] = (batch.embed_ragged(frames, tiles, b, alpha), batch.sigma1_map_ragged(frames, b))
+
+    arms = {
+        "two_pass": two_pass,
+        "with_key": lambda: state.__setitem__("with_key", batch.embed_with_key_ragged(frames, tiles, b, alpha)),
+        "embed": lambda: state.__setitem__("embed", batch.embed_ragged(frames, tiles, b, alpha)),
+    }
+    for fn in arms.values():
+        fn()
+    torch.cuda.synchronize()
+    for i in range(n):
+        assert torch.equal(state["two_pass"][0][i], state["with_key"][0][i]), ("embed differs", i)
+        assert torch.equal(state["two_pass"][1][i].view(torch.int32), state["with_key"][1][i].view(torch.int32)), ("key differs", i)
+    se, sm, sk = {}, {}, {}
+    batch.embed_ragged(frames, tiles, b, alpha, stats=se)
+    batch.sigma1_map_ragged(frames, b, stats=sm)
+    batch.embed_with_key_ragged(frames, tiles, b, alpha, stats=sk)
+    extra = {"block": b, "megapixels": round(sum(h * w for h, w in picks) / 1e6, 1), "outputs_equal": True,
+             "lapack_blocks_embed": se["lapack_blocks"], "lapack_blocks_map": sm["lapack_blocks"], "lapack_blocks_with_key": sk["lapack_blocks"]}
+    return [compare("E1", {"base": arms["two_pass"], "ragged": arms["with_key"]}, 10, rounds,
+                    {"what": "64 images enrolment: embed_with_key_ragged vs embed_ragged + sigma1_map_ragged (base)", **extra}),
+            compare("E2", {"base": arms["embed"], "ragged": arms["with_key"]}, 10, rounds,
+                    {"what": "64 images enrolment: embed_with_key_ragged vs embed_ragged alone (base)", **extra})]
+
+
 def workload_b(rounds, dev, n):
     out = []
     for cover in ("noise", "photo"):
@@ -173,7 +208,7 @@ def workload_b(rounds, dev, n):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", default="ab", choices=("a", "b", "k", "ab", "abk"))
+    ap.add_argument("--workload", default="ab", choices=("a", "b", "k", "e", "ab", "abk"))
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--frames-b", type=int, default=256)
     a = ap.parse_args()
@@ -187,6 +222,8 @@ def main():
         workload_b(a.rounds, dev, a.frames_b)
     if "k" in a.workload:
         workload_k(a.rounds, dev)
+    if "e" in a.workload:
+        workload_e(a.rounds, dev)
 
 
 if __name__ == "__main__":
