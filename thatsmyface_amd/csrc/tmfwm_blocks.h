@@ -329,6 +329,41 @@ constexpr bool kColdSpecial = TMF_COLD_SPECIAL && B == 8 && !LIST;
 template <int B, bool LIST>
 constexpr bool kSplitPost = TMF_SPLIT_POST && B == 8 && !LIST;
 
+// svd3's forms (tmfwm_device.h: kSvdFlatFirst64, kSvdNormsOnce, kSvdVOnlyEnd), each the same bits
+// as the plain form (DESIGN.md 4 for the A/B of each alone and together).
+// The first f64 sweep branch-free: after Bjorck it rotates essentially every pair of every block
+// (tolerance 2^-100), so the branching form's wave-uniform branches skip nothing there and each
+// pair's join costs 8 v_mov_b64 on 32 f64 operations.  true peels the first sweep off the loop
+// in the branch-free form; the later sweeps keep the branches.  On for b = 8's strip kernels
+// (embed<8> -2.7..-3.2 % per 4K frame on noise covers, 254 VGPRs, no scratch); its list pass runs
+// 1 % of the blocks and the other sizes are untimed.
+#ifndef TMF_FLAT_FIRST64
+#define TMF_FLAT_FIRST64 true
+#endif
+template <int B, bool LIST>
+constexpr bool kFlatFirst64 = TMF_FLAT_FIRST64 && B == 8 && !LIST;
+
+// Norms once: F and the first sweep's norms from one set of dot products in both phases, and an
+// f64 sweep after a Newton try takes the try's diagonal of G.  Dead update: phase 1's last round
+// of its last sweep rotates V32 alone (svd3 reads only V32 after it).  Both pass the register
+// gate at b = 8 and each alone gains (-0.7 %, -0.45 %), but beside the flat first sweep neither
+// does: norms once +-0 on embed<8> and +2.3 ms on the benchmark's step, the dead update +0.6 %.
+// Off everywhere.
+#ifndef TMF_NORMS_ONCE
+#define TMF_NORMS_ONCE false
+#endif
+template <int B, bool LIST>
+constexpr bool kNormsOnce = TMF_NORMS_ONCE && B == 8 && !LIST;
+#ifndef TMF_V_ONLY_END
+#define TMF_V_ONLY_END false
+#endif
+template <int B, bool LIST>
+constexpr bool kVOnlyEnd = TMF_V_ONLY_END && B == 8 && !LIST;
+
+template <int B, bool LIST>
+constexpr int kSvdForm = (kNormsOnce<B, LIST> ? kSvdNormsOnce : 0) | (kVOnlyEnd<B, LIST> ? kSvdVOnlyEnd : 0) |
+                         (kFlatFirst64<B, LIST> ? kSvdFlatFirst64 : 0);
+
 // b = 10 / 14 keep the reconstruction's fma chains in their (k-outer) source order: left free,
 // the compiler regroups them per output element and spills every element of Bm it reads
 // ahead of its use (272 / 282 VGPRs spilled -> 0 / 5; embed<14> 613 -> 360 us per 4K frame,
@@ -380,7 +415,7 @@ TMF_DEVI void embed_blocks(const EmbedArgs &a, const StripPos &pos, uint32_t id,
     // :195 (SVD); svd3's scratch and (b = 16) the parked D in the block's tile
     static_assert(!kPark || kParkOff<L> + B * B <= TS, "parked D fits the tile");
     bool slow = false;  // strip pass: this block was left to the list pass
-    svd3<B, L, kPark>(x, A, V, q, stamp, tile, tile + kParkOff<L>, !LIST && a.slow_list ? kDeferMax<B> : 0, &slow);
+    svd3<B, L, kPark, kSvdForm<B, LIST>>(x, A, V, q, stamp, tile, tile + kParkOff<L>, !LIST && a.slow_list ? kDeferMax<B> : 0, &slow);
     if (slow && pos.valid && q == 0) {
         const uint32_t row = blockIdx.y * (uint32_t)a.nbh + (uint32_t)pos.bi, s = row % kListShards;
         a.slow_list[shard_base(s, (uint32_t)a.nframes * (uint32_t)a.nbh, (uint32_t)a.nbw) +

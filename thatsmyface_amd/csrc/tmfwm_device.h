@@ -896,23 +896,15 @@ TMF_DEVI double rsqrt_c(double x)
 }
 TMF_DEVI float rsqrt_c(float x) { return __builtin_amdgcn_rsqf(x); }
 
-// Columns i, j of A (and V) <- (c x - s y, s x + c y) as fma(-s, y, c*x), fma(s, x, c*y)
-template <int R, int B, bool WANT_V, typename T>
-TMF_DEVI void rotate_cols(T (&A)[R][B], T (&V)[R][B], int i, int j, T c, T sn)
+// Columns i, j of A <- (c x - s y, s x + c y) as fma(-s, y, c*x), fma(s, x, c*y)
+template <int R, int B, typename T>
+TMF_DEVI void rotate_cols(T (&A)[R][B], int i, int j, T c, T sn)
 {
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const T x = A[r][i], y = A[r][j];
         A[r][i] = fma_t(-sn, y, c * x);
         A[r][j] = fma_t(sn, x, c * y);
-    }
-    if constexpr (WANT_V) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const T x = V[r][i], y = V[r][j];
-            V[r][i] = fma_t(-sn, y, c * x);
-            V[r][j] = fma_t(sn, x, c * y);
-        }
     }
 }
 
@@ -995,18 +987,33 @@ TMF_DEVI void lds_order() { asm volatile("" ::: "memory"); }
 // the values leave this point in order: the arithmetic producing them is not moved past it
 TMF_DEVI void pin_order(float &a, float &b) { asm volatile("" : "+v"(a), "+v"(b)); }
 
-// One sweep (oracle jacobi_sweep() / the loop body of jacobi()): nrm are recomputed, the
+// The column norms of A in the contract order (oracle: cdot(A, k, k) for k ascending), on
+// every lane of the block
+template <typename T, int B, int L>
+TMF_DEVI void col_norms(const T (&A)[(B + L - 1) / L][B], T (&nrm)[B])
+{
+    // batches of dot products: all lane-local chains first, then all cross-lane sums,
+    // so that the chains interleave and no DPP read waits on the write just before it
+    static_for<B>([&](auto K) { nrm[K] = cdot_part<kRows<B, L>, B>(A, K, K); });
+    static_for<B>([&](auto K) { nrm[K] = group_sum<L>(nrm[K]); });
+}
+
+// One sweep (oracle jacobi_sweep() / the loop body of jacobi()): from the column norms of A
+// (nrm: col_norms(A), the caller's -- a sweep's first step in the oracle), the
 // b-1 rounds of b/2 disjoint pairs rotate every pair that passes the tests.  `enable`
 // (same on the L lanes of a block) adds "skip" to every test of this block's pairs: a
 // disabled block takes the identity on every pair, bitwise.  Returns 1 on a lane that
 // rotated one of its own pairs (group_or over the block = the block rotated).
-template <typename T, int B, int L, bool WANT_V>
-TMF_DEVI int jacobi_sweep(T (&A)[(B + L - 1) / L][B], T (&V)[(B + L - 1) / L][B], int q, T *nl, T c2, T c2a, bool enable)
+// BRANCHY: see JacP.  a_dead (wave-uniform): nothing reads A or the norms after this sweep,
+// so its last round rotates V alone.
+template <typename T, int B, int L, bool WANT_V, bool BRANCHY>
+TMF_DEVI int jacobi_sweep(T (&A)[(B + L - 1) / L][B], T (&V)[(B + L - 1) / L][B], int q, T *nl, T (&nrm)[B], T c2, T c2a,
+                          bool enable, bool a_dead = false)
 {
     using P = JacP<T>;
     // NP pairs per round; lane q evaluates pairs [q*PP, q*PP + PP) that exist
     constexpr int R = kRows<B, L>, NP = B / 2, PP = (NP + L - 1) / L;
-    constexpr bool kBranchy = P::kBranchy;
+    constexpr bool kBranchy = BRANCHY;
     constexpr bool kLN = kLdsNorms<L, T>;
     constexpr bool kLB = kLdsBcast<L>;
     static_assert(!kLN || NP <= 8, "LDS norms: 4-bit pair table");
@@ -1024,11 +1031,6 @@ TMF_DEVI int jacobi_sweep(T (&A)[(B + L - 1) / L][B], T (&V)[(B + L - 1) / L][B]
         // b = 14 has no spill to remove and measured +1 %)
         asm volatile("" : "+v"(q));
     }
-    T nrm[B];
-    // batches of dot products: all lane-local chains first, then all cross-lane sums,
-    // so that the chains interleave and no DPP read waits on the write just before it
-    static_for<B>([&](auto K) { nrm[K] = cdot_part<R, B>(A, K, K); });
-    static_for<B>([&](auto K) { nrm[K] = group_sum<L>(nrm[K]); });
     if constexpr (kLN) {
         lds_order();
         if (q == 0) static_for<B>([&](auto K) { nl[K] = nrm[K]; });
@@ -1130,14 +1132,17 @@ TMF_DEVI int jacobi_sweep(T (&A)[(B + L - 1) / L][B], T (&V)[(B + L - 1) / L][B]
             // A (phase 3) and V can hold (their fma chains start from +0 and never make
             // -0), and A32 / phase-1 A only feed cdot(), which ignores signs of zero.
             if (!kBranchy || (own_ball[u] & kMemberMask<L, src>) != 0) {
-                if constexpr (!kLN) {
-                    T tg;
-                    if constexpr (kLB) tg = prm[16 + p];
-                    else tg = group_bcast<L, src>(mine[u].tg);
-                    nrm[i] = nrm[i] - tg;
-                    nrm[j] = nrm[j] + tg;
+                if (s < B - 2 || !a_dead) {  // (wave-uniform; the norms in LDS are the owner's, above)
+                    if constexpr (!kLN) {
+                        T tg;
+                        if constexpr (kLB) tg = prm[16 + p];
+                        else tg = group_bcast<L, src>(mine[u].tg);
+                        nrm[i] = nrm[i] - tg;
+                        nrm[j] = nrm[j] + tg;
+                    }
+                    rotate_cols<R, B>(A, i, j, c, sn);
                 }
-                rotate_cols<R, B, WANT_V>(A, V, i, j, c, sn);
+                if constexpr (WANT_V) rotate_cols<R, B>(V, i, j, c, sn);
             }
         });
     });
@@ -1153,11 +1158,40 @@ TMF_DEVI T frob2(const T (&A)[(B + L - 1) / L][B])
     return F;
 }
 
-template <typename T, int B, int L, bool WANT_V>
+// The same F from the column norms: the sum of frob2(), from +0, k ascending
+template <typename T, int B>
+TMF_DEVI T norm_sum(const T (&nrm)[B])
+{
+    T F = T(0);
+    static_for<B>([&](auto K) { F += nrm[K]; });
+    return F;
+}
+
+// svd3's forms (a kernel's choice, tmfwm_blocks.h; the same bits in every form):
+// kSvdNormsOnce: F and the first sweep's norms come from one set of dot products, and an f64
+//   sweep that follows a Newton try takes that try's diagonal of G for its norms -- A has not
+//   changed since unless the block took the step, and then it is done (2-lane blocks; the
+//   larger ones keep G in LDS and form the norms again).  Otherwise every sweep's norms are
+//   formed ahead of it, as the oracle's sweep does.
+// kSvdVOnlyEnd: phase 1's sweep of index max_sweeps - 1 rotates V32 alone in its last round:
+//   svd3 reads only V32 after phase 1.
+// kSvdFlatFirst64: phase 3's first sweep in the branch-free form (JacP), peeled off the loop.
+constexpr int kSvdNormsOnce = 1, kSvdVOnlyEnd = 2, kSvdFlatFirst64 = 4;
+
+// V_ONLY_END: the caller reads only V afterwards (A is left as the last sweep's last round found it)
+template <typename T, int B, int L, bool WANT_V, bool NORMS_ONCE = false, bool V_ONLY_END = false>
 TMF_DEVI int jacobi(T (&A)[(B + L - 1) / L][B], T (&V)[(B + L - 1) / L][B], int q, T *nl = nullptr)
 {
     using P = JacP<T>;
-    const T F = frob2<T, B, L>(A);
+    static_assert(!V_ONLY_END || WANT_V, "V is the result");
+    T nrm[B];
+    T F;
+    if constexpr (NORMS_ONCE) {
+        col_norms<T, B, L>(A, nrm);
+        F = norm_sum<T, B>(nrm);
+    } else {
+        F = frob2<T, B, L>(A);
+    }
     const T c2 = P::kC2 * F;
     T c2a = T(0);
     bool live = true;
@@ -1167,11 +1201,14 @@ TMF_DEVI int jacobi(T (&A)[(B + L - 1) / L][B], T (&V)[(B + L - 1) / L][B], int 
     }
     int count = 0;
     bool active = live;
-    for (int sweep = 0; sweep < P::max_sweeps(B); ++sweep) {
-        const int rotated = jacobi_sweep<T, B, L, WANT_V>(A, V, q, nl, c2, c2a, live);
+    for (int sweep = 0;;) {
+        if constexpr (!NORMS_ONCE) col_norms<T, B, L>(A, nrm);
+        const bool last = sweep == P::max_sweeps(B) - 1;
+        const int rotated = jacobi_sweep<T, B, L, WANT_V, P::kBranchy>(A, V, q, nl, nrm, c2, c2a, live, V_ONLY_END && last);
         count += active ? 1 : 0;
         active = active && group_or<L>(rotated) != 0;  // block rotated a pair this sweep
-        if (!__any(rotated)) break;
+        if (!__any(rotated) || ++sweep == P::max_sweeps(B)) break;
+        if constexpr (NORMS_ONCE) col_norms<T, B, L>(A, nrm);
     }
     return count;
 }
@@ -1323,13 +1360,13 @@ TMF_DEVI float newton_f(double g, double gi, double gj, double c2)
 // and lane 1 F_(p+1) -- each summing the couple's partial dot products in the butterfly's
 // operand order (p0 + p1 and p1 + p0 are the same bits) -- and the two swap F by one DPP
 // move, so the tests and the IEEE divides run once per pair instead of on both lanes.
+// G: on return the diagonal of G = col_norms(A) of the A the try found (the next sweep's norms
+// where the block does not take the step).
 template <int B, int L>
-TMF_DEVI bool newton_try(double (&A)[(B + L - 1) / L][B], double (&V)[(B + L - 1) / L][B], double c2, bool enable)
+TMF_DEVI bool newton_try(double (&A)[(B + L - 1) / L][B], double (&V)[(B + L - 1) / L][B], double c2, bool enable, double (&G)[B])
 {
     constexpr int R = kRows<B, L>, NP = B * (B - 1) / 2;
-    double G[B];
-    static_for<B>([&](auto K) { G[K] = cdot_part<R, B>(A, K, K); });
-    static_for<B>([&](auto K) { G[K] = group_sum<L>(G[K]); });
+    col_norms<double, B, L>(A, G);
     float F[NP], fmx = 0.0f;
     int ok = enable ? 1 : 0;
     if constexpr (L == 2) {
@@ -1567,31 +1604,57 @@ TMF_DEVI bool newton_try_lds(double (&A)[(B + L - 1) / L][B], double (&V)[(B + L
 // one of them -- the list pass redoes those from their pixels with the whole loop, so their
 // bits are those of the uninterrupted loop (a block's arithmetic never depends on the other
 // blocks of its wave).
-template <int B, int L>
+// NORMS_ONCE, FLAT_FIRST: svd3's forms (kSvdNormsOnce, kSvdFlatFirst64).
+template <int B, int L, bool NORMS_ONCE = false, bool FLAT_FIRST = false>
 TMF_DEVI int jacobi_newton(double (&A)[(B + L - 1) / L][B], double (&V)[(B + L - 1) / L][B], int q, double *nl = nullptr,
                            int defer_max = 0, bool *unfinished = nullptr)
 {
-    const double c2 = JacP<double>::kC2 * frob2<double, B, L>(A);
+    double nrm[B];  // NORMS_ONCE: the next sweep's norms, carried from the try (or formed) before it
+    double F;
+    if constexpr (NORMS_ONCE) {
+        col_norms<double, B, L>(A, nrm);
+        F = norm_sum<double, B>(nrm);
+    } else {
+        F = frob2<double, B, L>(A);
+    }
+    const double c2 = JacP<double>::kC2 * F;
     bool active = true;
     int sweeps = 0, newton = 0;
-    for (int it = 0; it < JacP<double>::kMaxSweeps; ++it) {
-        const int rotated = jacobi_sweep<double, B, L, true>(A, V, q, nl, c2, 0.0, active);
+    // one iteration: a sweep and its Newton try; true when the wave stops
+    auto step = [&](auto branchy) {
+        if constexpr (!NORMS_ONCE) col_norms<double, B, L>(A, nrm);
+        const int rotated = jacobi_sweep<double, B, L, true, decltype(branchy)::value>(A, V, q, nl, nrm, c2, 0.0, active);
         sweeps += active ? 1 : 0;
         active = active && group_or<L>(rotated) != 0;
-        if (!__any(active)) break;
+        if (!__any(active)) return true;
         bool took;
-        if constexpr (L >= 4) took = newton_try_lds<B, L>(A, V, c2, active, q, nl);
-        else took = newton_try<B, L>(A, V, c2, active);
+        if constexpr (L >= 4) {
+            took = newton_try_lds<B, L>(A, V, c2, active, q, nl);
+        } else if constexpr (NORMS_ONCE) {
+            took = newton_try<B, L>(A, V, c2, active, nrm);
+        } else {
+            double G[B];
+            took = newton_try<B, L>(A, V, c2, active, G);
+        }
         if (took) {
             newton = 1;
             active = false;
         }
-        if (!__any(active)) break;
+        if (!__any(active)) return true;
         if (defer_max > 0 && __builtin_popcountll(__ballot(active && q == 0)) <= defer_max) {
             if (unfinished) *unfinished = active;
-            break;
+            return true;
         }
-    }
+        if constexpr (NORMS_ONCE && L >= 4) col_norms<double, B, L>(A, nrm);
+        return false;
+    };
+    // FLAT_FIRST: after Bjorck the first sweep rotates essentially every pair in every block
+    // (the test's tolerance is 2^-100), so its wave-uniform branches skip nothing and their joins
+    // cost register copies; a block that skips a pair takes the identity there as in the taken
+    // branches (jacobi_sweep).  The later sweeps converge and keep the branches.
+    bool stop = false;
+    if constexpr (FLAT_FIRST) stop = step(std::false_type{});
+    for (int it = FLAT_FIRST ? 1 : 0; !stop && it < JacP<double>::kMaxSweeps; ++it) stop = step(std::true_type{});
     return sweeps | (newton << 16);
 }
 
@@ -1698,11 +1761,12 @@ constexpr int kScratchFloats = L <= 2 ? 2 : kNwtTable<B, L> + (B - 1) * (B / 2);
 // parameter slots), instead of in 32-36 registers that the f32 phase needs.
 template <int L>
 constexpr int kParkOff = L == 8 ? 32 : 0;
-template <int B, int L, bool PARK = false, typename Stamp = NoStamp>
+template <int B, int L, bool PARK = false, int FORM = 0, typename Stamp = NoStamp>
 TMF_DEVI int svd3(const float (&D)[(B + L - 1) / L][B], double (&A)[(B + L - 1) / L][B], double (&V)[(B + L - 1) / L][B], int q,
                   Stamp stamp = {}, void *nl = nullptr, float *park = nullptr, int defer_max = 0, bool *unfinished = nullptr)
 {
     constexpr int R = kRows<B, L>;
+    constexpr bool kOnce = (FORM & kSvdNormsOnce) != 0;
     if constexpr (PARK) {
 #pragma unroll
         for (int r = 0; r < R; ++r)
@@ -1720,7 +1784,7 @@ TMF_DEVI int svd3(const float (&D)[(B + L - 1) / L][B], double (&A)[(B + L - 1) 
                 A32[r][c] = D[r][c];
                 V32[r][c] = (q * R + r == c) ? 1.0f : 0.0f;
             }
-        s32 = jacobi<float, B, L, true>(A32, V32, q, static_cast<float *>(nl));
+        s32 = jacobi<float, B, L, true, kOnce, (FORM & kSvdVOnlyEnd) != 0>(A32, V32, q, static_cast<float *>(nl));
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -1743,7 +1807,7 @@ TMF_DEVI int svd3(const float (&D)[(B + L - 1) / L][B], double (&A)[(B + L - 1) 
     stamp(2);
     lds_order();
     int s64;
-    s64 = jacobi_newton<B, L>(A, V, q, static_cast<double *>(nl), defer_max, unfinished);
+    s64 = jacobi_newton<B, L, kOnce, (FORM & kSvdFlatFirst64) != 0>(A, V, q, static_cast<double *>(nl), defer_max, unfinished);
     stamp(3);
     return s64 | (s32 << 8);
 }

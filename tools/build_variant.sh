@@ -3,7 +3,7 @@
 # -> ab/libtmfwm_<name>.so (git-ignored; travels to the GPU box; load it with TMFWM_LIB).
 # The kernel TUs take the extra flags; with FALLBACK=1 in the environment the dgesdd-route
 # TU (tmfwm_fallback.hip) is recompiled with them too, otherwise the ABI / tile / QR /
-# dgesdd-route objects and the ragged calls' objects are the main build's (make -C
+# dgesdd-route objects and the ragged / keyed / embed-key calls' objects are the main build's (make -C
 # thatsmyface_amd/csrc first).
 # E8SCHED=<strategy> overrides the machine scheduler of the embed<8> TU (default max-ilp).
 # SRC_SED='<sed script>' compiles the kernel TUs from a copy of the sources edited by that
@@ -59,6 +59,6 @@ fi
 wait
 mkdir -p "$ROOT/ab"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$ROOT/ab/libtmfwm_$NAME.so" "$T/k.o" "$T/e8.o" "$T/r1.o" $R1L \
-    "$C/tmfwm_capi.o" "$C/tmfwm_multi.o" "$C/tmfwm_qr.o" "$C/tmfwm_tile.o" "$C/tmfwm_pixels.o" $FB "$C"/tmfwm_ragged*.o -fopenmp -ldl -lpthread
+    "$C/tmfwm_capi.o" "$C/tmfwm_multi.o" "$C/tmfwm_qr.o" "$C/tmfwm_tile.o" "$C/tmfwm_pixels.o" $FB "$C"/tmfwm_ragged*.o "$C"/tmfwm_keyed*.o "$C"/tmfwm_embed_key*.o -fopenmp -ldl -lpthread
 rm -rf "$T"
 echo "ab/libtmfwm_$NAME.so"
