@@ -12,6 +12,9 @@
 # instead (e.g. the build before a change, for an A/B on one box).  SRC_DIR=<dir> compiles the
 # kernel TUs from a copy of the csrc tree kept elsewhere (e.g. a git worktree with an
 # experimental edit).  NOMAKE=1 skips the main build's make (its objects are linked as they are).
+# ALL=1 (with SRC_SED, SRC_REV or SRC_DIR; no extra flags) builds EVERY translation unit from that
+# copy through the product's Makefile: for an edit to a header that the keyed, ragged or
+# dgesdd-route objects include too (e.g. sigma1_certified's margins, extract_byte).
 set -euo pipefail
 NAME=$1; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
@@ -33,6 +36,16 @@ elif [ -n "${SRC_SED:-}" ]; then
   cp "$C"/*.h "$C"/*.hip "$K"/
   cp "$ROOT"/include/*.h "$T/include/"
   sed -i "$SRC_SED" "$K"/*.h "$K"/*.hip
+fi
+if [ "${ALL:-0}" = "1" ]; then
+  [ "$K" != "$C" ] && [ $# -eq 0 ] || { echo "ALL=1 takes SRC_SED, SRC_REV or SRC_DIR and no extra flags" >&2; exit 2; }
+  cp -n "$C"/*.cpp "$C"/Makefile "$K"/
+  mkdir -p "$T/tools" "$ROOT/ab"
+  cp "$ROOT/tools/kernel_ids.py" "$T/tools/"
+  make -s -C "$K" -j8 OUT="$ROOT/ab/libtmfwm_$NAME.so" >/dev/null
+  rm -rf "$T"
+  echo "ab/libtmfwm_$NAME.so"
+  exit 0
 fi
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize -Wall $*"
 /opt/rocm/bin/hipcc $F -c "$K/tmfwm_kernels.hip" -o "$T/k.o" &
