@@ -177,7 +177,8 @@ int tmfwm_extract_route(const uint8_t *wm_rgb, const uint8_t *orig_rgb, int64_t 
  * np.linalg.svd's float32 S[0] on every route, so keys do not depend on the route.
  * *n_lapack_blocks, tmfwm_last_list_pass_blocks(), the non-convergence report, TMFWM_MEM_HOST
  * staging and TMFWM_MEM_DEVICE asynchrony as tmfwm_extract_route; with TMFWM_MEM_DEVICE the
- * output must not overlap an input.  Pixels are 3 bytes (TMFWM_PIX_RGB).
+ * output must not overlap an input.  Pixels are 3 bytes (TMFWM_PIX_RGB); tmfwm_sigma1_map_px and
+ * tmfwm_extract_keyed_px below take 4-byte pixels as well.
  */
 int tmfwm_sigma1_map(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
                      int32_t block, float *out_key, int32_t mem_kind, void *hip_stream, int32_t route,
@@ -191,6 +192,27 @@ int tmfwm_extract_keyed(const uint8_t *wm_rgb, int64_t n_frames, int32_t height,
 #define TMFWM_PIX_RGBX 4 /* 4 bytes per pixel, R G B pad: how PIL holds a mode-"RGB" image in memory
                             (Image.__arrow_c_array__ / Image.fromarrow share it without a copy);
                             the pad byte is ignored on input and written as 255 */
+
+/*
+ * tmfwm_sigma1_map and tmfwm_extract_keyed with a pixel layout (added within ABI 10; the version
+ * number is unchanged and existing entry points keep their behaviour): the frames hold
+ * pixel_bytes per pixel (TMFWM_PIX_RGB or TMFWM_PIX_RGBX; anything else is TMFWM_ERR_INVALID)
+ * and lie frame_stride bytes apart, frame_stride >= height*width*pixel_bytes.  Key bits and tile
+ * bytes are exactly those of the 3-byte call on the same R, G, B values; the pad byte is ignored.
+ * The keyed calls only read pixels, so 4-byte frames are read where they lie: kernels of their own
+ * take the R G B pad rows (whole dwords at every block size once the frames' base and
+ * frame_stride are multiples of 4, bytes otherwise), and with TMFWM_MEM_HOST the frames are
+ * staged as they are -- no pack launch and no 3-byte staging buffer.  With pixel_bytes == 3 each
+ * call is its sibling above.  Routes, *n_lapack_blocks, tmfwm_last_list_pass_blocks(), the
+ * non-convergence report, chunking, key_stride, the overlap rule and the alignment of out_key /
+ * key (4 bytes) as there; all arguments are checked before the device is touched.
+ */
+int tmfwm_sigma1_map_px(const uint8_t *rgb, int32_t pixel_bytes, int64_t frame_stride, int64_t n_frames, int32_t height,
+                        int32_t width, int32_t block, float *out_key, int32_t mem_kind, void *hip_stream, int32_t route,
+                        int64_t *n_lapack_blocks);
+int tmfwm_extract_keyed_px(const uint8_t *wm_rgb, int32_t pixel_bytes, int64_t frame_stride, int64_t n_frames, int32_t height,
+                           int32_t width, const float *key, int64_t key_stride, int32_t block, double alpha,
+                           uint8_t *out_tiles, int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
 
 /*
  * tmfwm_embed_route with a pixel layout per side (ABI 8): the input frames have
@@ -230,7 +252,8 @@ int tmfwm_embed_tiles(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_fra
  * One descriptor per frame.  The descriptor array itself is always host memory, whatever
  * mem_kind says about the pointers inside it; the library copies it before it returns, so the
  * caller may free or reuse it at once (also after an asynchronous TMFWM_MEM_DEVICE call).
- * Pixels are 3 bytes (TMFWM_PIX_RGB), rows packed: height x width x 3 bytes per image; the tile
+ * Pixels are 3 bytes (TMFWM_PIX_RGB; the keyed *_ragged_px calls below take 4 as well), rows
+ * packed: height x width x 3 bytes per image; the tile
  * is (height/block) x (width/block) bytes, packed.  A frame with height < block or
  * width < block has no block: embed writes its colour round trip, extract writes nothing for
  * it.  A frame with height == 0 or width == 0 is skipped (its pointers are not looked at).
@@ -319,6 +342,20 @@ int tmfwm_extract_keyed_ragged(const tmfwm_keyed_frame *frames, int64_t n_frames
                                int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
 
 /*
+ * The same two calls with a pixel layout (added within ABI 10): one layout per call, every image
+ * height x width x pixel_bytes, rows packed (TMFWM_PIX_RGB or TMFWM_PIX_RGBX; anything else is
+ * TMFWM_ERR_INVALID).  The descriptors are unchanged.  4-byte images are read where they lie, as
+ * tmfwm_sigma1_map_px reads them (dwords for an image whose pointer is 4-byte aligned, bytes
+ * otherwise); key bits and tile bytes are those of the 3-byte call on the same R, G, B values.
+ * With pixel_bytes == 3 each call is its sibling above.
+ */
+int tmfwm_sigma1_map_ragged_px(const tmfwm_key_frame *frames, int64_t n_frames, int32_t block, int32_t pixel_bytes,
+                               int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
+int tmfwm_extract_keyed_ragged_px(const tmfwm_keyed_frame *frames, int64_t n_frames, int32_t block, double alpha,
+                                  int32_t pixel_bytes, int32_t mem_kind, void *hip_stream, int32_t route,
+                                  int64_t *n_lapack_blocks);
+
+/*
  * Embed that also returns the extraction key (added within ABI 10; the version number is
  * unchanged and existing entry points keep their behaviour): the enrolment side of keyed
  * extraction in one call.  `out` receives exactly tmfwm_embed_route's bytes (per-frame tiles as
@@ -341,12 +378,27 @@ int tmfwm_extract_keyed_ragged(const tmfwm_keyed_frame *frames, int64_t n_frames
  * with TMFWM_MEM_DEVICE, disjoint from rgb, wm_tiles and out (TMFWM_ERR_INVALID otherwise).  A
  * frame size without a block gets its colour round trip and no key entry (out_key is not looked
  * at).  Memory kinds (TMFWM_MEM_HOST stages the keys back with the pixels), chunking, the count
- * and the non-convergence report as tmfwm_embed_route.  Pixels are 3 bytes (TMFWM_PIX_RGB).
+ * and the non-convergence report as tmfwm_embed_route.  Pixels are 3 bytes (TMFWM_PIX_RGB);
+ * tmfwm_embed_key_px takes a pixel layout per side.
  */
 int tmfwm_embed_key(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
                     const uint8_t *wm_tiles, int64_t tile_stride, int32_t block, double alpha, uint8_t *out,
                     float *out_key, int64_t key_stride, int32_t mem_kind, void *hip_stream, int32_t route,
                     int64_t *n_lapack_blocks);
+
+/*
+ * tmfwm_embed_key with a pixel layout per side (added within ABI 10): the arguments of
+ * tmfwm_embed_tiles, plus out_key and key_stride as tmfwm_embed_key has them.  `out` receives
+ * tmfwm_embed_tiles' bytes (pad 255 on 4-byte output) and out_key tmfwm_sigma1_map's key of the
+ * R, G, B values in `rgb`.  The call writes pixels, so 4-byte frames are converted on the device
+ * as in tmfwm_embed_tiles, and the key comes out of the embed passes over the packed frames.
+ * 3 -> 3 is tmfwm_embed_key (one frame stride for both).  key_stride, out_key's alignment and
+ * pixel_bytes are checked before the device is touched.
+ */
+int tmfwm_embed_key_px(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_frame_stride, int64_t n_frames, int32_t height,
+                       int32_t width, const uint8_t *wm_tiles, int64_t tile_stride, int32_t block, double alpha, uint8_t *out,
+                       int32_t out_pixel_bytes, int64_t out_frame_stride, float *out_key, int64_t key_stride,
+                       int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
 
 /*
  * The same over a ragged batch: tmfwm_embed_ragged's frames, each with a key output.  Frame i's

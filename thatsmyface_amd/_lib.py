@@ -124,6 +124,13 @@ SIGNATURES = {
     "tmfwm_extract_keyed_ragged": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _VP, _I32, _VP]),
     "tmfwm_embed_key": (ctypes.c_int, [_VP, _I64, _I32, _I32, _I64, _VP, _I64, _I32, _D, _VP, _VP, _I64, _I32, _VP, _I32, _VP]),
     "tmfwm_embed_key_ragged": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _VP, _I32, _VP]),
+    # the keyed calls with a pixel layout (3 or 4 bytes per pixel)
+    "tmfwm_sigma1_map_px": (ctypes.c_int, [_VP, _I32, _I64, _I64, _I32, _I32, _I32, _VP, _I32, _VP, _I32, _VP]),
+    "tmfwm_extract_keyed_px": (ctypes.c_int, [_VP, _I32, _I64, _I64, _I32, _I32, _VP, _I64, _I32, _D, _VP, _I32, _VP, _I32, _VP]),
+    "tmfwm_embed_key_px": (ctypes.c_int, [_VP, _I32, _I64, _I64, _I32, _I32, _VP, _I64, _I32, _D, _VP, _I32, _I64, _VP, _I64, _I32,
+                                          _VP, _I32, _VP]),
+    "tmfwm_sigma1_map_ragged_px": (ctypes.c_int, [_VP, _I64, _I32, _I32, _I32, _VP, _I32, _VP]),
+    "tmfwm_extract_keyed_ragged_px": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _I32, _VP, _I32, _VP]),
     "tmfwm_extract_px": (ctypes.c_int, [_VP, _I32, _I64, _VP, _I32, _I64, _I64, _I32, _I32, _I32, _D, _VP, _I32, _VP, _I32, _VP]),
     "tmfwm_embed_multi": (ctypes.c_int, [_VP, _I64, _I32, _I32, _I64, _VP, _I32, _D, _VP, _VP, _I32, _VP]),
     "tmfwm_release_cached_buffers": (ctypes.c_int, []),

@@ -21,11 +21,14 @@ def _stream(stream) -> int:
     return int(s.cuda_stream)
 
 
-def _check_frames(t: torch.Tensor, name: str) -> None:
+def _check_frames(t: torch.Tensor, name: str, px=(3,)) -> None:
+    """px: the pixel sizes the call takes -- (3,), or (3, 4) for the keyed calls, which also read
+    R G B pad frames (the pad byte is ignored)."""
     if not t.is_cuda:
         raise ValueError(f"{name} must be a GPU tensor")
-    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3:
-        raise ValueError(f"{name} must be (N, H, W, 3) uint8, got {tuple(t.shape)} {t.dtype}")
+    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] not in px:
+        want = " or ".join(f"(N, H, W, {p})" for p in px)
+        raise ValueError(f"{name} must be {want} uint8, got {tuple(t.shape)} {t.dtype}")
     if not t.is_contiguous():
         raise ValueError(f"{name} must be contiguous")
 
@@ -115,9 +118,10 @@ def sigma1_map(frames: torch.Tensor, block: int = 8, out: torch.Tensor | None = 
                stats: dict | None = None, route: str = "hybrid") -> torch.Tensor:
     """The extraction key of every frame: float32 (N, H//b, W//b), f32(sigma_1) of each block's
     DCT -- all that extract uses of an original image.  The key is the same bit
-    for bit on every route.  stats and route as extract_batch's."""
-    _check_frames(frames, "frames")
-    n, h, w, _ = frames.shape
+    for bit on every route.  frames is (N, H, W, 3), or (N, H, W, 4) R G B pad, which is read
+    in place and gives the key of its R, G, B values.  stats and route as extract_batch's."""
+    _check_frames(frames, "frames", (3, 4))
+    n, h, w, px = frames.shape
     if block not in SUPPORTED_BLOCK_SIZES:
         raise NotImplementedError(f"block {block}")
     shape = (n, h // block, w // block)
@@ -128,8 +132,8 @@ def sigma1_map(frames: torch.Tensor, block: int = 8, out: torch.Tensor | None = 
     cnt, ptr = _count_ptr(stats)
     with torch.cuda.device(frames.device):
         L = _lib.load()
-        _lib.check(L.tmfwm_sigma1_map(frames.data_ptr(), n, h, w, h * w * 3, block, out.data_ptr(), _lib.MEM_DEVICE,
-                                      _stream(stream), _lib.route_code(route), ptr), "sigma1_map")
+        _lib.check(L.tmfwm_sigma1_map_px(frames.data_ptr(), px, h * w * px, n, h, w, block, out.data_ptr(), _lib.MEM_DEVICE,
+                                         _stream(stream), _lib.route_code(route), ptr), "sigma1_map")
     if stats is not None:
         stats["lapack_blocks"] = int(cnt.value)
         stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks())
@@ -141,10 +145,10 @@ def extract_keyed(wframes: torch.Tensor, key: torch.Tensor, block: int = 8, alph
                   route: str = "hybrid") -> torch.Tensor:
     """extract_batch without the original frames: key is sigma1_map of the original(s), (H//b, W//b)
     shared by every frame (one original, many watermarked copies) or (N, H//b, W//b).  The
-    bytes are extract_batch's.  A key belongs to one block size and one image size.  stats and
-    route as extract_batch's."""
-    _check_frames(wframes, "wframes")
-    n, h, w, _ = wframes.shape
+    bytes are extract_batch's.  A key belongs to one block size and one image size.  wframes is
+    (N, H, W, 3), or (N, H, W, 4) R G B pad, read in place.  stats and route as extract_batch's."""
+    _check_frames(wframes, "wframes", (3, 4))
+    n, h, w, px = wframes.shape
     if block not in SUPPORTED_BLOCK_SIZES:
         raise NotImplementedError(f"block {block}")
     nbh, nbw = h // block, w // block
@@ -162,9 +166,9 @@ def extract_keyed(wframes: torch.Tensor, key: torch.Tensor, block: int = 8, alph
     cnt, ptr = _count_ptr(stats)
     with torch.cuda.device(wframes.device):
         L = _lib.load()
-        _lib.check(L.tmfwm_extract_keyed(wframes.data_ptr(), n, h, w, h * w * 3, key.data_ptr(),
-                                         0 if key.dim() == 2 else nbh * nbw * 4, block, float(alpha), out.data_ptr(),
-                                         _lib.MEM_DEVICE, _stream(stream), _lib.route_code(route), ptr), "extract_keyed")
+        _lib.check(L.tmfwm_extract_keyed_px(wframes.data_ptr(), px, h * w * px, n, h, w, key.data_ptr(),
+                                            0 if key.dim() == 2 else nbh * nbw * 4, block, float(alpha), out.data_ptr(),
+                                            _lib.MEM_DEVICE, _stream(stream), _lib.route_code(route), ptr), "extract_keyed")
     if stats is not None:
         stats["lapack_blocks"] = int(cnt.value)
         stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks())
@@ -180,9 +184,10 @@ def embed_with_key(frames: torch.Tensor, wm_tile: torch.Tensor, block: int = 8, 
     `out`.  On the hybrid and reference routes the key comes out of the embed passes themselves
     (DESIGN.md 5); on the rank-1 routes the call runs the map's passes after the embed's.
     wm_tile, stats and route as embed_batch's; "lapack_blocks" counts a block whose key the
-    dgesdd route had to decide as well."""
-    _check_frames(frames, "frames")
-    n, h, w, _ = frames.shape
+    dgesdd route had to decide as well.  frames may be (N, H, W, 4) R G B pad: the output then is
+    4-byte as well, pad 255 (or whatever layout `out` has), converted on the device."""
+    _check_frames(frames, "frames", (3, 4))
+    n, h, w, px = frames.shape
     if block not in SUPPORTED_BLOCK_SIZES:
         raise NotImplementedError(f"block {block}")
     nbh, nbw = h // block, w // block
@@ -192,9 +197,10 @@ def embed_with_key(frames: torch.Tensor, wm_tile: torch.Tensor, block: int = 8, 
     if out is None:
         out = torch.empty_like(frames)
     else:
-        _check_frames(out, "out")
-        if out.shape != frames.shape:
+        _check_frames(out, "out", (3, 4))
+        if out.shape[:3] != frames.shape[:3]:
             raise ValueError("out shape mismatch")
+    opx = out.shape[-1]
     shape = (n, nbh, nbw)
     if key_out is None:
         key_out = torch.empty(shape, dtype=torch.float32, device=frames.device)
@@ -204,24 +210,31 @@ def embed_with_key(frames: torch.Tensor, wm_tile: torch.Tensor, block: int = 8, 
     cnt, ptr = _count_ptr(stats)
     with torch.cuda.device(frames.device):
         L = _lib.load()
-        _lib.check(L.tmfwm_embed_key(frames.data_ptr(), n, h, w, h * w * 3, wm_tile.data_ptr(),
-                                     0 if wm_tile.dim() == 2 else nbh * nbw, block, float(alpha), out.data_ptr(),
-                                     key_out.data_ptr(), nbh * nbw * 4, _lib.MEM_DEVICE, _stream(stream), _lib.route_code(route), ptr),
-                   "embed_with_key")
+        _lib.check(L.tmfwm_embed_key_px(frames.data_ptr(), px, h * w * px, n, h, w, wm_tile.data_ptr(),
+                                        0 if wm_tile.dim() == 2 else nbh * nbw, block, float(alpha), out.data_ptr(), opx, h * w * opx,
+                                        key_out.data_ptr(), nbh * nbw * 4, _lib.MEM_DEVICE, _stream(stream), _lib.route_code(route),
+                                        ptr), "embed_with_key")
     if stats is not None:
         stats["lapack_blocks"] = int(cnt.value)
         stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks())
     return out, key_out
 
 
-def _check_ragged(frames, name: str, device=None):
-    """A sequence of (H_i, W_i, 3) uint8 contiguous GPU tensors on one device -> (list, device)."""
+def _check_ragged(frames, name: str, device=None, px=(3,)):
+    """A sequence of (H_i, W_i, 3) uint8 contiguous GPU tensors on one device -> (list, device).
+    px = (3, 4): the keyed calls, which take (H_i, W_i, 4) R G B pad frames as well -- one layout per
+    call, looked at before anything else about the tensors."""
     frames = list(frames)
+    if len(px) > 1:
+        sizes = {int(t.shape[-1]) for t in frames if isinstance(t, torch.Tensor) and t.dim() == 3 and t.shape[-1] in px}
+        if len(sizes) > 1:
+            raise ValueError(f"{name} mixes 3- and 4-byte pixels: one pixel layout per call")
     for i, t in enumerate(frames):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
             raise ValueError(f"{name}[{i}] must be a GPU tensor")
-        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[-1] != 3:
-            raise ValueError(f"{name}[{i}] must be (H, W, 3) uint8, got {tuple(t.shape)} {t.dtype}")
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[-1] not in px:
+            want = " or ".join(f"(H, W, {p})" for p in px)
+            raise ValueError(f"{name}[{i}] must be {want} uint8, got {tuple(t.shape)} {t.dtype}")
         if not t.is_contiguous():
             raise ValueError(f"{name}[{i}] must be contiguous")
         device = t.device if device is None else device
@@ -355,7 +368,8 @@ def _check_ragged_out(out, shapes, dtype, dev, what: str) -> list:
 
 def sigma1_map_ragged(frames, block: int = 8, out=None, stream=None, stats: dict | None = None, route: str = "hybrid") -> list:
     """The extraction keys of frames of mixed sizes by one set of launches
-    (tmfwm_sigma1_map_ragged): frames[i] is (H_i, W_i, 3) uint8, contiguous, all on one GPU.
+    (tmfwm_sigma1_map_ragged_px): frames[i] is (H_i, W_i, 3) uint8 -- or every frame (H_i, W_i, 4)
+    R G B pad, read in place; a mix is a ValueError -- contiguous, all on one GPU.
     Returns per-frame float32 (H_i // block, W_i // block) keys, views of one device allocation
     (or `out`, a sequence of such tensors); key i is sigma1_map(frames[i][None], ...)[0] bit for
     bit.  stats and route ("hybrid" / "reference") as sigma1_map's; no list pass runs, so
@@ -365,7 +379,8 @@ def sigma1_map_ragged(frames, block: int = 8, out=None, stream=None, stats: dict
     if block not in SUPPORTED_BLOCK_SIZES:
         raise NotImplementedError(f"block {block}")
     code = _ragged_route(route)
-    frames, dev = _check_ragged(frames, "frames")
+    frames, dev = _check_ragged(frames, "frames", px=(3, 4))
+    px = int(frames[0].shape[-1]) if frames else 3
     shapes = [(f.shape[0] // block, f.shape[1] // block) for f in frames]
     if out is None:  # float32 views of the one uint8 allocation: its pieces start on 16-byte boundaries
         out = [v.view(torch.float32).view(shapes[i]) for i, v in enumerate(
@@ -379,8 +394,8 @@ def sigma1_map_ragged(frames, block: int = 8, out=None, stream=None, stats: dict
     L = _lib.load()
     if frames:
         with torch.cuda.device(dev):
-            _lib.check(L.tmfwm_sigma1_map_ragged(ctypes.addressof(desc), len(frames), block, _lib.MEM_DEVICE, _stream(stream),
-                                                 code, ptr), "sigma1_map_ragged")
+            _lib.check(L.tmfwm_sigma1_map_ragged_px(ctypes.addressof(desc), len(frames), block, px, _lib.MEM_DEVICE,
+                                                    _stream(stream), code, ptr), "sigma1_map_ragged")
     if stats is not None:
         stats["lapack_blocks"] = int(cnt.value)
         stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks()) if frames else 0
@@ -427,7 +442,8 @@ def extract_keyed_ragged(wframes, keys, block: int = 8, alpha: float = 0.1, out=
     appear several times (one original, many watermarked copies).  Returns per-frame uint8 tiles,
     views of one device allocation (or `out`); tile i is the bytes of
     extract_keyed(wframes[i][None], keys[i], ...)[0], which are extract_batch's with the original.
-    A key belongs to one block size and one image size.  stats and route as sigma1_map_ragged's."""
+    A key belongs to one block size and one image size.  The frames are (H_i, W_i, 3), or all of
+    them (H_i, W_i, 4) R G B pad, read in place.  stats and route as sigma1_map_ragged's."""
     import ctypes
 
     if block not in SUPPORTED_BLOCK_SIZES:
@@ -443,7 +459,8 @@ def extract_keyed_ragged(wframes, keys, block: int = 8, alpha: float = 0.1, out=
         if isinstance(w, torch.Tensor) and w.dim() == 3 and tuple(k.shape) != (w.shape[0] // block, w.shape[1] // block):
             raise ValueError(f"keys[{i}] must be {(w.shape[0] // block, w.shape[1] // block)} for block {block} and a "
                              f"{w.shape[1]}x{w.shape[0]} frame, got {tuple(k.shape)}: a key belongs to one block size and one image size")
-    wframes, dev = _check_ragged(wframes, "wframes")
+    wframes, dev = _check_ragged(wframes, "wframes", px=(3, 4))
+    px = int(wframes[0].shape[-1]) if wframes else 3
     shapes = [(w.shape[0] // block, w.shape[1] // block) for w in wframes]
     for i, k in enumerate(keys):
         if k.device != dev or not k.is_contiguous():
@@ -459,8 +476,8 @@ def extract_keyed_ragged(wframes, keys, block: int = 8, alpha: float = 0.1, out=
     L = _lib.load()
     if wframes:
         with torch.cuda.device(dev):
-            _lib.check(L.tmfwm_extract_keyed_ragged(ctypes.addressof(desc), len(wframes), block, float(alpha), _lib.MEM_DEVICE,
-                                                    _stream(stream), code, ptr), "extract_keyed_ragged")
+            _lib.check(L.tmfwm_extract_keyed_ragged_px(ctypes.addressof(desc), len(wframes), block, float(alpha), px,
+                                                       _lib.MEM_DEVICE, _stream(stream), code, ptr), "extract_keyed_ragged")
     if stats is not None:
         stats["lapack_blocks"] = int(cnt.value)
         stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks()) if wframes else 0

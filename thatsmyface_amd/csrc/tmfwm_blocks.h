@@ -35,24 +35,29 @@ using Stamp = NoStamp;
 
 // Lanes per block L (== oracle jac_chunks): a power of two for the DPP butterflies,
 // with R = ceil(B/L) rows per lane (rows past B are zero padding).
-template <int B>
+// PX: bytes per pixel of the frames a kernel reads -- 3 (R G B), or 4 (R G B pad: the keyed
+// kernels' in-place reading of RGBX frames), where a block row is B whole dwords.
+template <int B, int PX = 3>
 struct Geo {
+    static_assert(PX == 3 || PX == 4, "pixel bytes");
     static constexpr int L = B == 4 ? 1 : B <= 8 ? 2 : B <= 12 ? 4 : 8;
     static constexpr int R = kRows<B, L>;          // rows per lane
     static constexpr int BPW = 64 / L;             // blocks per wave
-    static constexpr int NBYTES = B * 3;           // bytes per pixel row of a block
+    static constexpr int NBYTES = B * PX;          // bytes per pixel row of a block
     static constexpr int NW = (NBYTES + 3) / 4;    // u32 words holding them
-    static constexpr bool WORDS = NBYTES % 4 == 0; // dword I/O possible (b = 4, 8, 12, 16)
+    static constexpr bool WORDS = NBYTES % 4 == 0; // dword I/O possible (PX = 3: b = 4, 8, 12, 16; PX = 4: every b)
 };
 static_assert(Geo<6>::L == 2 && Geo<10>::L == 4 && Geo<14>::L == 8 && Geo<14>::R == 2, "lane layout");
+static_assert(Geo<6, 4>::WORDS && Geo<14, 4>::NW == 14 && !Geo<6>::WORDS, "4-byte pixels: a row is B dwords");
 
 // ---- byte rows: dword I/O when the row segment is whole dwords and aligned,
-// otherwise bytes (b = 6, 10, 14: 18, 30, 42 bytes per row)
-template <int B>
-TMF_DEVI void load_words(const uint8_t *p, bool aligned, uint32_t (&w)[Geo<B>::NW])
+// otherwise bytes (PX = 3 at b = 6, 10, 14: 18, 30, 42 bytes per row; the pad byte of a 4-byte
+// pixel is not read on the byte path)
+template <int B, int PX = 3>
+TMF_DEVI void load_words(const uint8_t *p, bool aligned, uint32_t (&w)[Geo<B, PX>::NW])
 {
-    constexpr int NW = Geo<B>::NW, NB = Geo<B>::NBYTES;
-    if (Geo<B>::WORDS && aligned) {
+    constexpr int NW = Geo<B, PX>::NW, NB = Geo<B, PX>::NBYTES;
+    if (Geo<B, PX>::WORDS && aligned) {
         const uint32_t *q = reinterpret_cast<const uint32_t *>(p);
 #pragma unroll
         for (int i = 0; i < NW; ++i) w[i] = q[i];
@@ -62,7 +67,7 @@ TMF_DEVI void load_words(const uint8_t *p, bool aligned, uint32_t (&w)[Geo<B>::N
             uint32_t v = 0;
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                if (4 * i + k < NB) v |= (uint32_t)p[4 * i + k] << (8 * k);
+                if (4 * i + k < NB && (PX == 3 || k < 3)) v |= (uint32_t)p[4 * i + k] << (8 * k);
             w[i] = v;
         }
     }
@@ -193,31 +198,31 @@ TMF_DEVI StripPos strip_pos(int strips_per_row, int nbw)
 
 // Load this lane's R pixel rows of its block (garbage-free zeros for blocks past
 // the right edge of the block grid) and return luma rows.
-template <int B>
+template <int B, int PX = 3>
 TMF_DEVI void load_block_rows(const uint8_t *frame_base, int W, const StripPos &pos, int q, bool aligned,
-                              uint32_t (&words)[Geo<B>::R][Geo<B>::NW])
+                              uint32_t (&words)[Geo<B>::R][Geo<B, PX>::NW])
 {
     constexpr int R = Geo<B>::R;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         if (pos.valid && real_row<B>(q, r)) {
-            const uint8_t *p = frame_base + ((int64_t)(pos.bi * B + q * R + r) * W + (int64_t)pos.bj * B) * 3;
-            load_words<B>(p, aligned, words[r]);
+            const uint8_t *p = frame_base + ((int64_t)(pos.bi * B + q * R + r) * W + (int64_t)pos.bj * B) * PX;
+            load_words<B, PX>(p, aligned, words[r]);
         } else {
 #pragma unroll
-            for (int i = 0; i < Geo<B>::NW; ++i) words[r][i] = 0u;
+            for (int i = 0; i < Geo<B, PX>::NW; ++i) words[r][i] = 0u;
         }
     }
 }
 
-template <int B>
-TMF_DEVI void luma_rows(const uint32_t (&words)[Geo<B>::R][Geo<B>::NW], float (&y)[Geo<B>::R][B])
+template <int B, int PX = 3>
+TMF_DEVI void luma_rows(const uint32_t (&words)[Geo<B>::R][Geo<B, PX>::NW], float (&y)[Geo<B>::R][B])
 {
 #pragma unroll
     for (int r = 0; r < Geo<B>::R; ++r)
 #pragma unroll
         for (int c = 0; c < B; ++c) {
-            const uint32_t R8 = byte_at(words[r], 3 * c), G8 = byte_at(words[r], 3 * c + 1), B8 = byte_at(words[r], 3 * c + 2);
+            const uint32_t R8 = byte_at(words[r], PX * c), G8 = byte_at(words[r], PX * c + 1), B8 = byte_at(words[r], PX * c + 2);
             y[r][c] = luma(R8, G8, B8);
         }
 }

@@ -134,6 +134,16 @@ int check_frames(int64_t n, int32_t H, int32_t W, int64_t stride, int32_t block)
     return 0;
 }
 
+// check_frames for frames of px bytes per pixel (the keyed *_px entries): 3 is check_frames itself
+int check_frames_px(int64_t n, int32_t H, int32_t W, int32_t px, int64_t stride, int32_t block)
+{
+    if (px == TMFWM_PIX_RGB) return check_frames(n, H, W, stride, block);
+    if (px != TMFWM_PIX_RGBX) return fail(TMFWM_ERR_INVALID, "pixel bytes %d (3 or 4)", px);
+    if (int rc = check_frames(n, H, W, (int64_t)H * W * 3, block)) return rc;
+    if (stride < (int64_t)H * W * 4) return fail(TMFWM_ERR_INVALID, "frame_stride %lld < H*W*4", (long long)stride);
+    return 0;
+}
+
 // After argument validation: there is no CPU fallback, so no device is an error.
 int need_device()
 {
@@ -533,8 +543,8 @@ int run_extract(const ExtractArgs &a, hipStream_t st, const Report &rep, int rou
 }
 
 // Keyed extraction over device-resident frames (a.src, and a.key_out for the map or a.key / a.out
-// for the extract, set): as run_extract, on one image per frame.
-int run_keyed(const KeyedArgs &a, bool map, hipStream_t st, const Report &rep, int route)
+// for the extract, set): as run_extract, on one image per frame of px bytes per pixel.
+int run_keyed(const KeyedArgs &a, bool map, hipStream_t st, const Report &rep, int route, int px = 3)
 {
     Chunks ch;
     ch.plan(a.nframes, (int64_t)a.nbh * a.nbw);
@@ -550,8 +560,9 @@ int run_keyed(const KeyedArgs &a, bool map, hipStream_t st, const Report &rep, i
         }
         wire_lists(k, w);
         if (route == TMFWM_ROUTE_REFERENCE) TMF_HIP(launch_list_all(k.fb_list, k.fb_count, nb, st));
-        else TMF_HIP(map ? launch_sigma1_map(k, st) : launch_extract_keyed(k, st));
-        TMF_HIP(map ? launch_sigma1_fixup(k, k.fb_list, k.fb_count, nb, st) : launch_extract_keyed_fixup(k, k.fb_list, k.fb_count, nb, st));
+        else TMF_HIP(map ? launch_sigma1_map(k, st, px) : launch_extract_keyed(k, st, px));
+        TMF_HIP(map ? launch_sigma1_fixup(k, k.fb_list, k.fb_count, nb, st, px)
+                    : launch_extract_keyed_fixup(k, k.fb_list, k.fb_count, nb, st, px));
         return 0;
     });
 }
@@ -598,6 +609,13 @@ KeyedArgs keyed_args(int64_t n, int32_t H, int32_t W, int64_t stride, int32_t bl
 bool dev_aligned(const void *p, const void *q, int64_t stride, int W)
 {
     return ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(q)) % 4 == 0) && stride % 4 == 0 && W % 4 == 0;
+}
+
+// KeyedArgs::aligned of frames of px bytes per pixel: at 4 every pixel is a dword once the base
+// and the frame stride are multiples of 4, whatever W is
+bool keyed_aligned(const void *p, int64_t stride, int W, int px)
+{
+    return px == 4 ? reinterpret_cast<uintptr_t>(p) % 4 == 0 && stride % 4 == 0 : dev_aligned(p, p, stride, W);
 }
 
 int64_t count_chunks(int64_t nframes, int H, int W, int block)
@@ -669,7 +687,7 @@ int tmfwm_device_count(void)
 static int embed_rgb(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
                      const uint8_t *wm_tile, int64_t tile_stride, int32_t block, double alpha, uint8_t *out, int32_t mem_kind,
                      void *hip_stream, int32_t route, int64_t *n_lapack_blocks, bool with_key = false, float *out_key = nullptr,
-                     int64_t key_stride = 0)
+                     int64_t key_stride = 0, bool px_entry = false)
 {
     if (int rc = begin_call(route, n_lapack_blocks)) return rc;
     if (int rc = check_frames(n_frames, height, width, frame_stride, block)) return rc;
@@ -680,6 +698,8 @@ static int embed_rgb(const uint8_t *rgb, int64_t n_frames, int32_t height, int32
     if (with_key && n_frames > 1 && (key_stride % 4 != 0 || key_stride < kbytes))
         return fail(TMFWM_ERR_INVALID, "key_stride %lld: a multiple of 4 >= (H/block)*(W/block)*4 = %lld", (long long)key_stride,
                     (long long)kbytes);
+    // (tmfwm_embed_key_px checks the key pointer's alignment before the device is looked for)
+    if (px_entry && with_key && kbytes > 0 && reinterpret_cast<uintptr_t>(out_key) % 4) return fail(TMFWM_ERR_INVALID, "out_key is not 4-byte aligned");
     if (int rc = need_device()) return rc;
     if (n_frames == 0 || height == 0 || width == 0) return 0;
     with_key = with_key && kbytes > 0;  // no block: the colour round trip and no key entry
@@ -845,15 +865,19 @@ int tmfwm_extract(const uint8_t *wm_rgb, const uint8_t *orig_rgb, int64_t n_fram
 }
 
 // ---- keyed extraction (within ABI 10): the original's per-block f32 sigma_1 as a key
-int tmfwm_sigma1_map(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride, int32_t block,
-                     float *out_key, int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+// frames of px bytes per pixel, read where they lie (tmfwm_sigma1_map: 3; tmfwm_sigma1_map_px, which
+// also checks out_key's alignment before the device is looked for: px_entry)
+static int sigma1_map_frames(const uint8_t *rgb, int32_t px, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
+                             int32_t block, float *out_key, int32_t mem_kind, void *hip_stream, int32_t route,
+                             int64_t *n_lapack_blocks, bool px_entry)
 {
     if (int rc = begin_call(route, n_lapack_blocks)) return rc;
-    if (int rc = check_frames(n_frames, height, width, frame_stride, block)) return rc;
+    if (int rc = check_frames_px(n_frames, height, width, px, frame_stride, block)) return rc;
+    if (px_entry && reinterpret_cast<uintptr_t>(out_key) % 4) return fail(TMFWM_ERR_INVALID, "out_key is not 4-byte aligned");
     if (int rc = need_device()) return rc;
     const int64_t kbytes = (int64_t)(height / block) * (width / block) * 4;
     if (n_frames == 0 || kbytes == 0) return 0;
-    const size_t span = span_bytes(n_frames, frame_stride, (int64_t)height * width * 3), obytes = (size_t)(kbytes * n_frames);
+    const size_t span = span_bytes(n_frames, frame_stride, (int64_t)height * width * px), obytes = (size_t)(kbytes * n_frames);
     hipStream_t st = pick_stream(hip_stream);
     tmf::KeyedArgs a = tmf::keyed_args(n_frames, height, width, frame_stride, block, 1.0);
     if (mem_kind == TMFWM_MEM_DEVICE) {
@@ -863,8 +887,8 @@ int tmfwm_sigma1_map(const uint8_t *rgb, int64_t n_frames, int32_t height, int32
         if (ranges_overlap(out_key, obytes, rgb, span)) return fail(TMFWM_ERR_INVALID, "out_key overlaps the input batch");
         a.src = rgb;
         a.key_out = out_key;
-        a.aligned = tmf::dev_aligned(rgb, rgb, frame_stride, width);
-        return tmf::run_keyed(a, true, st, device_report(n_lapack_blocks), route);
+        a.aligned = tmf::keyed_aligned(rgb, frame_stride, width, px);
+        return tmf::run_keyed(a, true, st, device_report(n_lapack_blocks), route, px);
     }
     if (mem_kind != TMFWM_MEM_HOST) return fail(TMFWM_ERR_INVALID, "mem_kind %d", mem_kind);
     if (!rgb || !out_key) return fail(TMFWM_ERR_INVALID, "NULL host pointer");
@@ -874,27 +898,44 @@ int tmfwm_sigma1_map(const uint8_t *rgb, int64_t n_frames, int32_t height, int32
     TMF_HIP(hipMemcpyAsync(din.p, rgb, span, hipMemcpyHostToDevice, st));
     a.src = static_cast<const uint8_t *>(din.p);
     a.key_out = static_cast<float *>(dkey.p);
-    a.aligned = frame_stride % 4 == 0 && width % 4 == 0;
+    a.aligned = tmf::keyed_aligned(din.p, frame_stride, width, px);  // (the staging buffer is aligned)
     HostCall hc(tmf::count_chunks(n_frames, height, width, block), st, n_lapack_blocks);
-    if (int rc = tmf::run_keyed(a, true, st, hc.report(), route)) return rc;
+    if (int rc = tmf::run_keyed(a, true, st, hc.report(), route, px)) return rc;
     TMF_HIP(hipMemcpyAsync(out_key, dkey.p, obytes, hipMemcpyDeviceToHost, st));
     return hc.finish();
 }
 
-int tmfwm_extract_keyed(const uint8_t *wm_rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
-                        const float *key, int64_t key_stride, int32_t block, double alpha, uint8_t *out_tiles, int32_t mem_kind,
-                        void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+int tmfwm_sigma1_map(const uint8_t *rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride, int32_t block,
+                     float *out_key, int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    return sigma1_map_frames(rgb, TMFWM_PIX_RGB, n_frames, height, width, frame_stride, block, out_key, mem_kind, hip_stream, route,
+                             n_lapack_blocks, false);
+}
+
+int tmfwm_sigma1_map_px(const uint8_t *rgb, int32_t pixel_bytes, int64_t frame_stride, int64_t n_frames, int32_t height,
+                        int32_t width, int32_t block, float *out_key, int32_t mem_kind, void *hip_stream, int32_t route,
+                        int64_t *n_lapack_blocks)
+{
+    return sigma1_map_frames(rgb, pixel_bytes, n_frames, height, width, frame_stride, block, out_key, mem_kind, hip_stream, route,
+                             n_lapack_blocks, true);
+}
+
+static int extract_keyed_frames(const uint8_t *wm_rgb, int32_t px, int64_t n_frames, int32_t height, int32_t width,
+                                int64_t frame_stride, const float *key, int64_t key_stride, int32_t block, double alpha,
+                                uint8_t *out_tiles, int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks,
+                                bool px_entry)
 {
     if (int rc = begin_call(route, n_lapack_blocks)) return rc;
-    if (int rc = check_frames(n_frames, height, width, frame_stride, block)) return rc;
+    if (int rc = check_frames_px(n_frames, height, width, px, frame_stride, block)) return rc;
     if (!std::isfinite(alpha) || alpha == 0.0) return fail(TMFWM_ERR_INVALID, "alpha must be finite and non-zero");
     const int64_t tbytes = (int64_t)(height / block) * (width / block), kbytes = tbytes * 4;
     if (key_stride < 0 || key_stride % 4 != 0 || (key_stride != 0 && key_stride < kbytes))
         return fail(TMFWM_ERR_INVALID, "key_stride %lld: 0 (one shared key) or a multiple of 4 >= (H/block)*(W/block)*4 = %lld",
                     (long long)key_stride, (long long)kbytes);
+    if (px_entry && reinterpret_cast<uintptr_t>(key) % 4) return fail(TMFWM_ERR_INVALID, "key is not 4-byte aligned");
     if (int rc = need_device()) return rc;
     if (n_frames == 0 || tbytes == 0) return 0;
-    const size_t span = span_bytes(n_frames, frame_stride, (int64_t)height * width * 3), obytes = (size_t)(tbytes * n_frames);
+    const size_t span = span_bytes(n_frames, frame_stride, (int64_t)height * width * px), obytes = (size_t)(tbytes * n_frames);
     const size_t kspan = (size_t)((key_stride ? (n_frames - 1) * key_stride : 0) + kbytes);
     hipStream_t st = pick_stream(hip_stream);
     tmf::KeyedArgs a = tmf::keyed_args(n_frames, height, width, frame_stride, block, alpha);
@@ -909,8 +950,8 @@ int tmfwm_extract_keyed(const uint8_t *wm_rgb, int64_t n_frames, int32_t height,
         a.key = key;
         a.key_stride = key_stride / 4;
         a.out = out_tiles;
-        a.aligned = tmf::dev_aligned(wm_rgb, wm_rgb, frame_stride, width);
-        return tmf::run_keyed(a, false, st, device_report(n_lapack_blocks), route);
+        a.aligned = tmf::keyed_aligned(wm_rgb, frame_stride, width, px);
+        return tmf::run_keyed(a, false, st, device_report(n_lapack_blocks), route, px);
     }
     if (mem_kind != TMFWM_MEM_HOST) return fail(TMFWM_ERR_INVALID, "mem_kind %d", mem_kind);
     if (!wm_rgb || !key || !out_tiles) return fail(TMFWM_ERR_INVALID, "NULL host pointer");
@@ -924,11 +965,27 @@ int tmfwm_extract_keyed(const uint8_t *wm_rgb, int64_t n_frames, int32_t height,
     a.key = static_cast<const float *>(dkey.p);
     a.key_stride = key_stride ? tbytes : 0;
     a.out = static_cast<uint8_t *>(dout.p);
-    a.aligned = frame_stride % 4 == 0 && width % 4 == 0;
+    a.aligned = tmf::keyed_aligned(dw.p, frame_stride, width, px);  // (the staging buffer is aligned)
     HostCall hc(tmf::count_chunks(n_frames, height, width, block), st, n_lapack_blocks);
-    if (int rc = tmf::run_keyed(a, false, st, hc.report(), route)) return rc;
+    if (int rc = tmf::run_keyed(a, false, st, hc.report(), route, px)) return rc;
     TMF_HIP(hipMemcpyAsync(out_tiles, dout.p, obytes, hipMemcpyDeviceToHost, st));
     return hc.finish();
+}
+
+int tmfwm_extract_keyed(const uint8_t *wm_rgb, int64_t n_frames, int32_t height, int32_t width, int64_t frame_stride,
+                        const float *key, int64_t key_stride, int32_t block, double alpha, uint8_t *out_tiles, int32_t mem_kind,
+                        void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    return extract_keyed_frames(wm_rgb, TMFWM_PIX_RGB, n_frames, height, width, frame_stride, key, key_stride, block, alpha, out_tiles,
+                                mem_kind, hip_stream, route, n_lapack_blocks, false);
+}
+
+int tmfwm_extract_keyed_px(const uint8_t *wm_rgb, int32_t pixel_bytes, int64_t frame_stride, int64_t n_frames, int32_t height,
+                           int32_t width, const float *key, int64_t key_stride, int32_t block, double alpha, uint8_t *out_tiles,
+                           int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    return extract_keyed_frames(wm_rgb, pixel_bytes, n_frames, height, width, frame_stride, key, key_stride, block, alpha, out_tiles,
+                                mem_kind, hip_stream, route, n_lapack_blocks, true);
 }
 
 // ---- 4-byte pixels (ABI 8): the core runs on compact RGB device buffers; RGBX inputs are
@@ -972,17 +1029,19 @@ int device_rgb(const uint8_t *src, int32_t px, int64_t stride, int64_t n, int32_
 }  // namespace
 }  // extern "C++"
 
-int tmfwm_embed_tiles(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_frame_stride, int64_t n_frames, int32_t height,
-                      int32_t width, const uint8_t *wm_tiles, int64_t tile_stride, int32_t block, double alpha, uint8_t *out,
-                      int32_t out_pixel_bytes, int64_t out_frame_stride, int32_t mem_kind, void *hip_stream, int32_t route,
-                      int64_t *n_lapack_blocks)
+// tmfwm_embed_tiles, and with_key tmfwm_embed_key_px: frame f's key to out_key + f * key_stride bytes,
+// out of the embed passes over the packed 3-byte frames (run_embed with a.key_out)
+static int embed_layouts(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_frame_stride, int64_t n_frames, int32_t height,
+                         int32_t width, const uint8_t *wm_tiles, int64_t tile_stride, int32_t block, double alpha, uint8_t *out,
+                         int32_t out_pixel_bytes, int64_t out_frame_stride, int32_t mem_kind, void *hip_stream, int32_t route,
+                         int64_t *n_lapack_blocks, bool with_key, float *out_key, int64_t key_stride)
 {
     t_err.clear();
     const uint8_t *wm_tile = wm_tiles;
     if (in_pixel_bytes == TMFWM_PIX_RGB && out_pixel_bytes == TMFWM_PIX_RGB) {
         if (in_frame_stride != out_frame_stride) return fail(TMFWM_ERR_INVALID, "3-byte input and output need one frame_stride");
         return embed_rgb(rgb, n_frames, height, width, in_frame_stride, wm_tile, tile_stride, block, alpha, out, mem_kind, hip_stream,
-                         route, n_lapack_blocks);
+                         route, n_lapack_blocks, with_key, out_key, key_stride, with_key);
     }
     if (int rc = begin_call(route, n_lapack_blocks)) return rc;
     if (int rc = check_frames(n_frames, height, width, (int64_t)height * width * 3, block)) return rc;
@@ -992,8 +1051,16 @@ int tmfwm_embed_tiles(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_fra
     if (int rc = check_tile_stride(tile_stride, (int64_t)nbh * nbw)) return rc;
     if (!std::isfinite(alpha)) return fail(TMFWM_ERR_INVALID, "alpha is not finite");
     if (mem_kind != TMFWM_MEM_HOST && mem_kind != TMFWM_MEM_DEVICE) return fail(TMFWM_ERR_INVALID, "mem_kind %d", mem_kind);
+    const int64_t kbytes = (int64_t)nbh * nbw * 4;
+    if (with_key && n_frames > 1 && (key_stride % 4 != 0 || key_stride < kbytes))
+        return fail(TMFWM_ERR_INVALID, "key_stride %lld: a multiple of 4 >= (H/block)*(W/block)*4 = %lld", (long long)key_stride,
+                    (long long)kbytes);
+    if (with_key && kbytes > 0 && reinterpret_cast<uintptr_t>(out_key) % 4) return fail(TMFWM_ERR_INVALID, "out_key is not 4-byte aligned");
     if (int rc = need_device()) return rc;
     if (n_frames == 0 || height == 0 || width == 0) return 0;
+    with_key = with_key && kbytes > 0;  // no block: the colour round trip and no key entry
+    if (n_frames == 1) key_stride = kbytes;
+    const size_t kspan = with_key ? (size_t)((n_frames - 1) * key_stride + kbytes) : 0;
     const size_t tbytes = (size_t)nbh * nbw;
     const int64_t f3 = (int64_t)height * width * 3, fo = (int64_t)height * width * out_pixel_bytes;
     const size_t ospan = span_bytes(n_frames, out_frame_stride, fo);
@@ -1008,10 +1075,17 @@ int tmfwm_embed_tiles(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_fra
             if (tile_stride && ranges_overlap(wm_tile, span_bytes(n_frames, tile_stride, (int64_t)tbytes), out, ospan))
                 return fail(TMFWM_ERR_INVALID, "out overlaps wm_tile");
         }
-    } else if (!out || (tbytes && !wm_tile)) {
+        if (with_key) {
+            if (int rc = check_device_ptr(out_key, "out_key")) return rc;
+            if (ranges_overlap(out_key, kspan, rgb, span_bytes(n_frames, in_frame_stride, (int64_t)height * width * in_pixel_bytes)) ||
+                ranges_overlap(out_key, kspan, wm_tile, span_bytes(n_frames, tile_stride, (int64_t)tbytes)))
+                return fail(TMFWM_ERR_INVALID, "out_key's output overlaps an input of the call");
+            if (ranges_overlap(out_key, kspan, out, ospan)) return fail(TMFWM_ERR_INVALID, "out_key's output overlaps out");
+        }
+    } else if (!out || (tbytes && !wm_tile) || (with_key && !out_key)) {
         return fail(TMFWM_ERR_INVALID, "NULL host pointer");
     }
-    DevBuf src3, tmp, dst3, dst4, dwm;
+    DevBuf src3, tmp, dst3, dst4, dwm, dkey;
     const uint8_t *s3p = nullptr;
     int64_t s3 = 0;
     if (int rc = device_rgb(rgb, in_pixel_bytes, in_frame_stride, n_frames, height, width, mem_kind, st, "input frames", src3, tmp,
@@ -1029,6 +1103,14 @@ int tmfwm_embed_tiles(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_fra
     a.wm = wm;
     a.wm_stride = wm_stride;
     a.aligned = tmf::dev_aligned(a.src, a.dst, s3, width);
+    if (with_key && mem_kind == TMFWM_MEM_DEVICE) {
+        a.key_out = out_key;
+        a.key_stride = key_stride / 4;
+    } else if (with_key) {  // staged compact
+        if (int rc = dkey.alloc((size_t)(kbytes * n_frames), st, "sigma_1 key maps")) return rc;
+        a.key_out = static_cast<float *>(dkey.p);
+        a.key_stride = kbytes / 4;
+    }
     // the output's final layout (RGB or RGBX, the caller's stride) is made on the device, at `o`
     auto layout = [&](uint8_t *o) -> int {
         if (out_pixel_bytes == TMFWM_PIX_RGBX)
@@ -1042,7 +1124,8 @@ int tmfwm_embed_tiles(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_fra
         if (int rc = tmf::run_embed(a, st, device_report(n_lapack_blocks), route)) return rc;
         return layout(out);
     }
-    HostCall hc(tmf::count_chunks(n_frames, height, width, block), st, n_lapack_blocks);
+    const int64_t nch = tmf::count_chunks(n_frames, height, width, block);
+    HostCall hc(tmf::embed_key_composed(block, route, with_key) ? 2 * nch : nch, st, n_lapack_blocks);
     if (int rc = tmf::run_embed(a, st, hc.report(), route)) return rc;
     if (int rc = dst4.alloc(ospan, st, "output staging")) return rc;
     if (int rc = layout(static_cast<uint8_t *>(dst4.p))) return rc;
@@ -1051,7 +1134,28 @@ int tmfwm_embed_tiles(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_fra
     else
         TMF_HIP(hipMemcpy2DAsync(out, (size_t)out_frame_stride, dst4.p, (size_t)out_frame_stride, (size_t)fo, (size_t)n_frames,
                                  hipMemcpyDeviceToHost, st));
+    if (with_key)  // one copy, or one row per frame past the caller's padding
+        TMF_HIP(hipMemcpy2DAsync(out_key, (size_t)key_stride, dkey.p, (size_t)kbytes, (size_t)kbytes, (size_t)n_frames,
+                                 hipMemcpyDeviceToHost, st));
     return hc.finish();
+}
+
+int tmfwm_embed_tiles(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_frame_stride, int64_t n_frames, int32_t height,
+                      int32_t width, const uint8_t *wm_tiles, int64_t tile_stride, int32_t block, double alpha, uint8_t *out,
+                      int32_t out_pixel_bytes, int64_t out_frame_stride, int32_t mem_kind, void *hip_stream, int32_t route,
+                      int64_t *n_lapack_blocks)
+{
+    return embed_layouts(rgb, in_pixel_bytes, in_frame_stride, n_frames, height, width, wm_tiles, tile_stride, block, alpha, out,
+                         out_pixel_bytes, out_frame_stride, mem_kind, hip_stream, route, n_lapack_blocks, false, nullptr, 0);
+}
+
+int tmfwm_embed_key_px(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_frame_stride, int64_t n_frames, int32_t height,
+                       int32_t width, const uint8_t *wm_tiles, int64_t tile_stride, int32_t block, double alpha, uint8_t *out,
+                       int32_t out_pixel_bytes, int64_t out_frame_stride, float *out_key, int64_t key_stride, int32_t mem_kind,
+                       void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    return embed_layouts(rgb, in_pixel_bytes, in_frame_stride, n_frames, height, width, wm_tiles, tile_stride, block, alpha, out,
+                         out_pixel_bytes, out_frame_stride, mem_kind, hip_stream, route, n_lapack_blocks, true, out_key, key_stride);
 }
 
 int tmfwm_embed_px(const uint8_t *rgb, int32_t in_pixel_bytes, int64_t in_frame_stride, int64_t n_frames, int32_t height,
@@ -1459,7 +1563,8 @@ struct RFrame {
     uint8_t *out;
     int32_t H, W;
     uint8_t *out2 = nullptr;  // RKind::EmbedKey only
-    int64_t pixel_bytes() const { return (int64_t)H * W * 3; }
+    int32_t px = 3;           // bytes per pixel of in0 (4: the keyed *_ragged_px calls, one layout per call)
+    int64_t pixel_bytes() const { return (int64_t)H * W * px; }
     int64_t tile_bytes(int b) const { return (int64_t)(H / b) * (W / b); }
     // the bytes behind in1 and out
     int64_t in1_bytes(RKind k, int b) const
@@ -1496,7 +1601,7 @@ int check_ragged_call(const void *frames, int64_t n, int32_t block, double alpha
 // one frame's sizes and pointers (the tile and key pointers only where the frame has a block)
 int check_ragged_frame(int64_t i, const RFrame &f, int32_t block, RKind kind)
 {
-    if (int rc = check_frames(1, f.H, f.W, f.pixel_bytes(), block)) return fail(rc, "frame %lld: %s", (long long)i, t_err.c_str());
+    if (int rc = check_frames(1, f.H, f.W, (int64_t)f.H * f.W * 3, block)) return fail(rc, "frame %lld: %s", (long long)i, t_err.c_str());
     if (f.H == 0 || f.W == 0) return 0;
     if (f.tile_bytes(block) > 0x7FFFFFFFll) return fail(TMFWM_ERR_INVALID, "frame %lld: more than 2^31 - 1 blocks", (long long)i);
     const bool tile = f.tile_bytes(block) > 0;
@@ -1651,7 +1756,8 @@ void plan_ragged(const std::vector<RFrame> &fr, int32_t block, RKind kind, std::
         t.nbw = f.W / block;
         t.strips_per_row = (t.nbw + bpw - 1) / bpw;
         // the frame's pixel buffers: two of them, or the single one of the keyed calls
-        t.aligned = tmf::dev_aligned(f.in0, embeds(kind) ? f.out : kind == RKind::Extract ? f.in1 : f.in0, 0, f.W);
+        t.aligned = f.px == 4 ? (int32_t)tmf::keyed_aligned(f.in0, 0, f.W, 4)
+                              : (int32_t)tmf::dev_aligned(f.in0, embeds(kind) ? f.out : kind == RKind::Extract ? f.in1 : f.in0, 0, f.W);
         const int64_t waves = (int64_t)t.nbh * t.strips_per_row, blocks = (int64_t)t.nbh * t.nbw;
         const int64_t edge = embeds(kind) ? (int64_t)f.H * f.W - blocks * block * block : 0;
         if (blocks == 0 && edge == 0) continue;
@@ -1677,7 +1783,8 @@ void plan_ragged(const std::vector<RFrame> &fr, int32_t block, RKind kind, std::
 // chunks through two_pass, with the edge pass between a chunk's first pass and its fixup pass and
 // neither of the two for a chunk without a block.
 int run_ragged(int32_t block, double alpha, RKind kind, hipStream_t st, int route, const Report &rep,
-               const std::vector<tmf::RaggedFrame> &table, const std::vector<RaggedChunk> &chunks, const std::vector<float *> &keys)
+               const std::vector<tmf::RaggedFrame> &table, const std::vector<RaggedChunk> &chunks, const std::vector<float *> &keys,
+               int px = 3)  // px: the keyed kinds' bytes per pixel
 {
     if (chunks.empty()) return 0;
     // the frame table and behind it the key side table (RKind::EmbedKey; empty otherwise), one upload
@@ -1712,16 +1819,16 @@ int run_ragged(int32_t block, double alpha, RKind kind, hipStream_t st, int rout
                 TMF_HIP(kind == RKind::EmbedKey  ? tmf::launch_embed_key_ragged(r, k.waves, st)
                         : kind == RKind::Embed   ? tmf::launch_embed_ragged(r, k.waves, st)
                         : kind == RKind::Extract ? tmf::launch_extract_ragged(r, k.waves, st)
-                        : kind == RKind::Map     ? tmf::launch_sigma1_map_ragged(r, k.waves, st)
-                                                 : tmf::launch_extract_keyed_ragged(r, k.waves, st));
+                        : kind == RKind::Map     ? tmf::launch_sigma1_map_ragged(r, k.waves, st, px)
+                                                 : tmf::launch_extract_keyed_ragged(r, k.waves, st, px));
         }
         if (embeds(kind)) TMF_HIP(tmf::launch_edges_ragged(r, k.edge, st));
         if (k.blocks > 0)
             TMF_HIP(kind == RKind::EmbedKey  ? tmf::launch_embed_key_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st)
                     : kind == RKind::Embed   ? tmf::launch_embed_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st)
                     : kind == RKind::Extract ? tmf::launch_extract_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st)
-                    : kind == RKind::Map     ? tmf::launch_sigma1_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st)
-                                             : tmf::launch_extract_keyed_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st));
+                    : kind == RKind::Map     ? tmf::launch_sigma1_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st, px)
+                                             : tmf::launch_extract_keyed_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st, px));
         return 0;
     });
 }
@@ -1739,10 +1846,11 @@ int ragged_call(std::vector<RFrame> &fr, int32_t block, double alpha, RKind kind
     std::vector<tmf::RaggedFrame> table;
     std::vector<RaggedChunk> chunks;
     std::vector<float *> keys;
+    const int px = fr[0].px;  // one layout per call
     if (mem_kind == TMFWM_MEM_DEVICE) {
         if (int rc = check_ragged_device(fr, block, kind)) return rc;
         plan_ragged(fr, block, kind, table, chunks, keys);
-        return run_ragged(block, alpha, kind, st, route, device_report(n_lapack), table, chunks, keys);
+        return run_ragged(block, alpha, kind, st, route, device_report(n_lapack), table, chunks, keys, px);
     }
     // host memory: every buffer of the call in one device allocation (16-byte aligned pieces),
     // results copied back, one synchronisation
@@ -1773,7 +1881,7 @@ int ragged_call(std::vector<RFrame> &fr, int32_t block, double alpha, RKind kind
     }
     plan_ragged(dv, block, kind, table, chunks, keys);
     HostCall hc((int64_t)chunks.size(), st, n_lapack);
-    if (int rc = run_ragged(block, alpha, kind, st, route, hc.report(), table, chunks, keys)) return rc;
+    if (int rc = run_ragged(block, alpha, kind, st, route, hc.report(), table, chunks, keys, px)) return rc;
     for (size_t i = 0; i < fr.size(); ++i) {
         if (!fr[i].has_work(kind, block)) continue;
         TMF_HIP(hipMemcpyAsync(fr[i].out, dv[i].out, (size_t)fr[i].out_bytes(kind, block), hipMemcpyDeviceToHost, st));
@@ -1919,26 +2027,42 @@ int tmfwm_extract_ragged(const tmfwm_extract_frame *frames, int64_t n_frames, in
     return ragged_call(fr, block, alpha, RKind::Extract, mem_kind, hip_stream, route, n_lapack_blocks);
 }
 
-// keyed extraction over ragged batches: the key rides in the frame's in1 / out slot as bytes
+// keyed extraction over ragged batches: the key rides in the frame's in1 / out slot as bytes; every
+// frame of the call holds pixel_bytes bytes per pixel
+int tmfwm_sigma1_map_ragged_px(const tmfwm_key_frame *frames, int64_t n_frames, int32_t block, int32_t pixel_bytes, int32_t mem_kind,
+                               void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    if (int rc = check_ragged_call(frames, n_frames, block, 1.0, RKind::Map, mem_kind, route, n_lapack_blocks)) return rc;
+    if (pixel_bytes != TMFWM_PIX_RGB && pixel_bytes != TMFWM_PIX_RGBX) return fail(TMFWM_ERR_INVALID, "pixel bytes %d (3 or 4)", pixel_bytes);
+    std::vector<RFrame> fr((size_t)n_frames);
+    for (int64_t i = 0; i < n_frames; ++i)
+        fr[(size_t)i] = {frames[i].rgb, nullptr,    reinterpret_cast<uint8_t *>(frames[i].out_key), frames[i].height, frames[i].width,
+                         nullptr,       pixel_bytes};
+    return ragged_call(fr, block, 1.0, RKind::Map, mem_kind, hip_stream, route, n_lapack_blocks);
+}
+
 int tmfwm_sigma1_map_ragged(const tmfwm_key_frame *frames, int64_t n_frames, int32_t block, int32_t mem_kind, void *hip_stream,
                             int32_t route, int64_t *n_lapack_blocks)
 {
-    if (int rc = check_ragged_call(frames, n_frames, block, 1.0, RKind::Map, mem_kind, route, n_lapack_blocks)) return rc;
+    return tmfwm_sigma1_map_ragged_px(frames, n_frames, block, TMFWM_PIX_RGB, mem_kind, hip_stream, route, n_lapack_blocks);
+}
+
+int tmfwm_extract_keyed_ragged_px(const tmfwm_keyed_frame *frames, int64_t n_frames, int32_t block, double alpha, int32_t pixel_bytes,
+                                  int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    if (int rc = check_ragged_call(frames, n_frames, block, alpha, RKind::Keyed, mem_kind, route, n_lapack_blocks)) return rc;
+    if (pixel_bytes != TMFWM_PIX_RGB && pixel_bytes != TMFWM_PIX_RGBX) return fail(TMFWM_ERR_INVALID, "pixel bytes %d (3 or 4)", pixel_bytes);
     std::vector<RFrame> fr((size_t)n_frames);
     for (int64_t i = 0; i < n_frames; ++i)
-        fr[(size_t)i] = {frames[i].rgb, nullptr, reinterpret_cast<uint8_t *>(frames[i].out_key), frames[i].height, frames[i].width};
-    return ragged_call(fr, block, 1.0, RKind::Map, mem_kind, hip_stream, route, n_lapack_blocks);
+        fr[(size_t)i] = {frames[i].wm_rgb, reinterpret_cast<const uint8_t *>(frames[i].key), frames[i].out_tile, frames[i].height,
+                         frames[i].width,  nullptr, pixel_bytes};
+    return ragged_call(fr, block, alpha, RKind::Keyed, mem_kind, hip_stream, route, n_lapack_blocks);
 }
 
 int tmfwm_extract_keyed_ragged(const tmfwm_keyed_frame *frames, int64_t n_frames, int32_t block, double alpha, int32_t mem_kind,
                                void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
 {
-    if (int rc = check_ragged_call(frames, n_frames, block, alpha, RKind::Keyed, mem_kind, route, n_lapack_blocks)) return rc;
-    std::vector<RFrame> fr((size_t)n_frames);
-    for (int64_t i = 0; i < n_frames; ++i)
-        fr[(size_t)i] = {frames[i].wm_rgb, reinterpret_cast<const uint8_t *>(frames[i].key), frames[i].out_tile, frames[i].height,
-                         frames[i].width};
-    return ragged_call(fr, block, alpha, RKind::Keyed, mem_kind, hip_stream, route, n_lapack_blocks);
+    return tmfwm_extract_keyed_ragged_px(frames, n_frames, block, alpha, TMFWM_PIX_RGB, mem_kind, hip_stream, route, n_lapack_blocks);
 }
 
 int tmfwm_prepare_tiles_ragged(const tmfwm_tile_job *jobs, int64_t n_jobs, int32_t preserve_ratio, int32_t mem_kind,

@@ -52,12 +52,13 @@ constexpr int kFixLanes = B <= 8 ? 8 : 16;
 TMF_DEVI void group_sync() { asm volatile("" ::: "memory"); }
 
 // this block's luma, then its 2-D DCT (axis 0, then axis 1: watermarking.py:192, :279-282),
-// into t[B*B] (row-major) -- the group's lanes take pixels, then columns, then rows
-template <int B, int G>
+// into t[B*B] (row-major) -- the group's lanes take pixels, then columns, then rows; PX bytes
+// per pixel (Geo<B, PX>, tmfwm_blocks.h), read byte by byte at either size
+template <int B, int G, int PX = 3>
 TMF_DEVI void fix_load_dct(const uint8_t *frame, int W, int bi, int bj, float *t, int gl)
 {
     for (int k = gl; k < B * B; k += G) {
-        const uint8_t *p = frame + ((int64_t)(bi * B + k / B) * W + (int64_t)bj * B + k % B) * 3;
+        const uint8_t *p = frame + ((int64_t)(bi * B + k / B) * W + (int64_t)bj * B + k % B) * PX;
         t[k] = luma(p[0], p[1], p[2]);
     }
     group_sync();

@@ -87,7 +87,7 @@ struct KeyedArgs {
     int64_t tile_stride;
     int64_t key_stride;      // in floats
     int H, W, block, nbh, nbw, strips_per_row;
-    int aligned;
+    int aligned;             // 3-byte pixels: as ExtractArgs; 4-byte pixels: src and frame_stride are multiples of 4
     float alpha32;
     // the lists and counters of ExtractArgs, used the same way
     uint32_t *fb_list;
@@ -181,15 +181,19 @@ hipError_t embed_key_strips_b(const EmbedArgs &a, hipStream_t st);  // tmfwm_emb
 template <int B>
 hipError_t extract_fixup_b(const ExtractArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
 template <int B>
-hipError_t sigma1_fixup_b(const KeyedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
+hipError_t sigma1_fixup_b(const KeyedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st, int px);
 template <int B>
-hipError_t extract_keyed_fixup_b(const KeyedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
-// keyed extraction (tmfwm_keyed.hip; the dgesdd-route passes per block size: tmfwm_keyed_fixup.hip)
-hipError_t launch_sigma1_map(const KeyedArgs &a, hipStream_t st);
-hipError_t launch_extract_keyed(const KeyedArgs &a, hipStream_t st);
-hipError_t launch_sigma1_fixup(const KeyedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
+hipError_t extract_keyed_fixup_b(const KeyedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st,
+                                 int px);
+// keyed extraction (tmfwm_keyed.hip; the dgesdd-route passes per block size: tmfwm_keyed_fixup.hip).
+// px: bytes per pixel of the frames at a.src -- 3, or 4 (R G B pad) for the kernels that read
+// RGBX frames in place; a.aligned then means base and frame stride are multiples of 4
+hipError_t launch_sigma1_map(const KeyedArgs &a, hipStream_t st, int px = 3);
+hipError_t launch_extract_keyed(const KeyedArgs &a, hipStream_t st, int px = 3);
+hipError_t launch_sigma1_fixup(const KeyedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st,
+                               int px = 3);
 hipError_t launch_extract_keyed_fixup(const KeyedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries,
-                                      hipStream_t st);
+                                      hipStream_t st, int px = 3);
 // the reference route: list = 0 .. n-1, *count = n (every block of a launch on the dgesdd route)
 hipError_t launch_list_all(uint32_t *list, uint32_t *count, int64_t n, hipStream_t st);
 // RGBX (4 bytes per pixel, PIL's in-memory "RGB") <-> RGB (3 bytes) per frame (tmfwm_pixels.hip);

@@ -37,30 +37,32 @@ TMF_DEVI void keyed_store(const KeyedArgs &a, int64_t frame, int bi, int bj, flo
 template <int B>
 constexpr int kKeyedWaves = B > 8 ? 2 : kExtract8Waves;
 
-// sigma_1 of this wave's blocks of the one image (pos per lane), certified or not (ok)
-template <int B, int ITERS>
+// sigma_1 of this wave's blocks of the one image (pos per lane), certified or not (ok).  PX: the
+// frames' bytes per pixel (Geo<B, PX>); at PX = 4 a.aligned says that the frame base and the frame
+// stride are multiples of 4 -- every block row is then whole aligned dwords, whatever W is
+template <int B, int ITERS, int PX = 3>
 TMF_DEVI void keyed_sigma(const KeyedArgs &a, const StripPos &pos, float *tile, int q, float &s, bool &ok)
 {
     constexpr int R = Geo<B>::R, L = Geo<B>::L;
-    uint32_t w[R][Geo<B>::NW];
+    uint32_t w[R][Geo<B, PX>::NW];
     float x[1][R][B], s1[1];
     bool k[1];
-    load_block_rows<B>(a.src + pos.frame * a.frame_stride, a.W, pos, q, a.aligned, w);
-    dct_rows_of<B>(w, q, tile, x[0]);
+    load_block_rows<B, PX>(a.src + pos.frame * a.frame_stride, a.W, pos, q, a.aligned, w);
+    dct_rows_of<B, PX>(w, q, tile, x[0]);
     sigma1_certified<B, L, ITERS, 1>(x, s1, k);
     s = s1[0];
     ok = k[0];
 }
 
 // a listed block on the dgesdd route: S[0] of np.linalg.svd's arithmetic, stored as keyed_store has it
-template <int B, class Par, int G, bool MAP>
+template <int B, class Par, int G, bool MAP, int PX = 3>
 TMF_DEVI void keyed_fix_block(const KeyedArgs &a, uint32_t id, FixLdsS<B> &f, int gl)
 {
     const uint32_t per_frame = (uint32_t)a.nbh * (uint32_t)a.nbw;
     int64_t fr;
     int bi, bj;
     block_of(id, per_frame, a.nbw, fr, bi, bj);
-    fix_load_dct<B, G>(a.src + fr * a.frame_stride, a.W, bi, bj, f.D, gl);
+    fix_load_dct<B, G, PX>(a.src + fr * a.frame_stride, a.W, bi, bj, f.D, gl);
     const int info = lp::svd_f32_ws<false, Par>(f.D, runtime_n(B), nullptr, f.S, nullptr, f.ws);  // :279-282
     if (info && gl == 0 && a.fb_bad) atomicAdd(a.fb_bad, 1u);
     const float s = f.S[0];

@@ -4,6 +4,7 @@
 //
 //   sigma1_map_kernel      key[frame][bi][bj] = f32(sigma_1) of the block
 //   extract_keyed_kernel   out[frame][bi][bj] = extract_byte(sigma_1 of the block, key entry, alpha)
+//   sigma1_map_px4_kernel, extract_keyed_px4_kernel   the same on frames of 4-byte pixels (R G B pad)
 //
 // A block whose enclosure does not decide f32(sigma_1) goes to the list pass (kListPowerIters)
 // and from there to the dgesdd route (tmfwm_keyed_fixup.hip), as in the pair path.
@@ -12,7 +13,7 @@
 namespace tmf {
 
 // (kKeyedWaves and keyed_sigma, the strip body of one image: tmfwm_keyed.h)
-template <int B, bool LIST, bool MAP>
+template <int B, bool LIST, bool MAP, int PX = 3>
 TMF_DEVI void keyed_pass(const KeyedArgs &a)
 {
     constexpr int L = Geo<B>::L, BPW = Geo<B>::BPW, LD = B + 1;
@@ -35,7 +36,7 @@ TMF_DEVI void keyed_pass(const KeyedArgs &a)
                 pos.bj = (int)(rem % (uint32_t)a.nbw);
                 float s;
                 bool ok;
-                keyed_sigma<B, kListPowerIters>(a, pos, tile, q, s, ok);
+                keyed_sigma<B, kListPowerIters, PX>(a, pos, tile, q, s, ok);
                 if (pos.valid && q == 0) {
                     if (ok) keyed_store<MAP>(a, pos.frame, pos.bi, pos.bj, s);
                     else a.fb_list[atomicAdd(a.fb_count, 1u)] = id;  // dgesdd route
@@ -47,7 +48,7 @@ TMF_DEVI void keyed_pass(const KeyedArgs &a)
         const StripPos pos = strip_pos<B>(a.strips_per_row, a.nbw);
         float s;
         bool ok;
-        keyed_sigma<B, kPowerIters>(a, pos, tile, q, s, ok);
+        keyed_sigma<B, kPowerIters, PX>(a, pos, tile, q, s, ok);
         if (!pos.valid || q != 0) return;
         if (!ok) {  // the enclosure did not decide f32(sigma_1): list pass, or the dgesdd route
             const uint32_t id = (uint32_t)(((int64_t)blockIdx.y * a.nbh + pos.bi) * a.nbw + pos.bj);
@@ -75,31 +76,54 @@ __global__ __launch_bounds__(64, kKeyedWaves<B>) void extract_keyed_kernel(Keyed
     keyed_pass<B, LIST, false>(a);
 }
 
-// the strip pass, then the list pass over the whole chunk (ids relative to a.src)
+// The same passes over frames of 4-byte pixels (R G B pad), read where they lie: kernels of their
+// own, so that the 3-byte kernels above keep their names and their code.
+template <int B, bool LIST = false>
+__global__ __launch_bounds__(64, kKeyedWaves<B>) void sigma1_map_px4_kernel(KeyedArgs a)
+{
+    keyed_pass<B, LIST, true, 4>(a);
+}
+
+template <int B, bool LIST = false>
+__global__ __launch_bounds__(64, kKeyedWaves<B>) void extract_keyed_px4_kernel(KeyedArgs a)
+{
+    keyed_pass<B, LIST, false, 4>(a);
+}
+
+// the strip pass, then the list pass over the whole chunk (ids relative to a.src); px: the
+// frames' bytes per pixel (3 or 4: the callers have checked it)
 template <bool MAP>
-static hipError_t launch_keyed(const KeyedArgs &a, hipStream_t st)
+static hipError_t launch_keyed(const KeyedArgs &a, hipStream_t st, int px)
 {
     if (a.nbh == 0 || a.nbw == 0) return hipSuccess;
+    if (px != 3 && px != 4) return hipErrorInvalidValue;
     return for_block(a.block, [&](auto b) {
         constexpr int B = b();
+        if (px == 4) {
+            if constexpr (MAP) return launch_strips(a, Geo<B>::BPW, sigma1_map_px4_kernel<B, false>, sigma1_map_px4_kernel<B, true>, st);
+            else return launch_strips(a, Geo<B>::BPW, extract_keyed_px4_kernel<B, false>, extract_keyed_px4_kernel<B, true>, st);
+        }
         if constexpr (MAP) return launch_strips(a, Geo<B>::BPW, sigma1_map_kernel<B, false>, sigma1_map_kernel<B, true>, st);
         else return launch_strips(a, Geo<B>::BPW, extract_keyed_kernel<B, false>, extract_keyed_kernel<B, true>, st);
     });
 }
 
-hipError_t launch_sigma1_map(const KeyedArgs &a, hipStream_t st) { return launch_keyed<true>(a, st); }
-hipError_t launch_extract_keyed(const KeyedArgs &a, hipStream_t st) { return launch_keyed<false>(a, st); }
+hipError_t launch_sigma1_map(const KeyedArgs &a, hipStream_t st, int px) { return launch_keyed<true>(a, st, px); }
+hipError_t launch_extract_keyed(const KeyedArgs &a, hipStream_t st, int px) { return launch_keyed<false>(a, st, px); }
 
 // the dgesdd-route passes, one TU per block size (tmfwm_keyed_fixup.hip)
-hipError_t launch_sigma1_fixup(const KeyedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st)
+hipError_t launch_sigma1_fixup(const KeyedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st,
+                               int px)
 {
-    return for_block(a.block, [&](auto b) { return sigma1_fixup_b<b()>(a, list, count, max_entries, st); });
+    if (px != 3 && px != 4) return hipErrorInvalidValue;
+    return for_block(a.block, [&](auto b) { return sigma1_fixup_b<b()>(a, list, count, max_entries, st, px); });
 }
 
 hipError_t launch_extract_keyed_fixup(const KeyedArgs &a, const uint32_t *list, const uint32_t *count, int64_t max_entries,
-                                      hipStream_t st)
+                                      hipStream_t st, int px)
 {
-    return for_block(a.block, [&](auto b) { return extract_keyed_fixup_b<b()>(a, list, count, max_entries, st); });
+    if (px != 3 && px != 4) return hipErrorInvalidValue;
+    return for_block(a.block, [&](auto b) { return extract_keyed_fixup_b<b()>(a, list, count, max_entries, st, px); });
 }
 
 }  // namespace tmf

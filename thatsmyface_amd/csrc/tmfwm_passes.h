@@ -15,10 +15,10 @@ constexpr int kPowerIters = 3;
 constexpr int kListPowerIters = 8;
 constexpr int kExtract8Waves = 3;  // waves per SIMD the register allocation of extract<b <= 8> allows
 
-template <int B>
-TMF_DEVI void dct_rows_of(const uint32_t (&words)[Geo<B>::R][Geo<B>::NW], int q, float *tile, float (&x)[Geo<B>::R][B])
+template <int B, int PX = 3>
+TMF_DEVI void dct_rows_of(const uint32_t (&words)[Geo<B>::R][Geo<B, PX>::NW], int q, float *tile, float (&x)[Geo<B>::R][B])
 {
-    luma_rows<B>(words, x);
+    luma_rows<B, PX>(words, x);
     dct2d_rows_layout<B, false>(x, tile, q);
 }
 

@@ -22,7 +22,8 @@ struct RaggedFrame {
     uint8_t *out;        // embed: the output pixels; extract, keyed extract: the nbh x nbw tile; map: the nbh x nbw
                          // f32 key output (4-byte aligned, written as float *)
     int32_t H, W, nbh, nbw, strips_per_row;
-    int32_t aligned;     // as dev_aligned: the pixel buffers (both, or the one of the keyed calls) 4-byte aligned and W % 4 == 0
+    int32_t aligned;     // as dev_aligned: the pixel buffers (both, or the one of the keyed calls) 4-byte aligned and W % 4 == 0;
+                         // keyed calls on 4-byte pixels: the pixel buffer 4-byte aligned, whatever W is
     // exclusive prefix sums over the frames of the chunk (the launches' flat indices):
     uint32_t wave0;      // strip waves, nbh * strips_per_row per frame
     uint32_t block0;     // blocks, nbh * nbw per frame: the block-list ids are block0 + bi * nbw + bj
@@ -52,8 +53,9 @@ int ragged_strip_blocks(int block);
 // strip pass of a chunk: `waves` = the chunk's strip waves (> 0), one workgroup each
 hipError_t launch_embed_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st);
 hipError_t launch_extract_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st);
-hipError_t launch_sigma1_map_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st);
-hipError_t launch_extract_keyed_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st);
+// (px: the frames' bytes per pixel, one layout per call -- 3, or 4 for RGBX frames read in place)
+hipError_t launch_sigma1_map_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st, int px = 3);
+hipError_t launch_extract_keyed_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st, int px = 3);
 // embed's key variants: the strip pass and the dgesdd route, each storing its blocks' key entries
 hipError_t launch_embed_key_ragged(const RaggedKeyArgs &r, int64_t waves, hipStream_t st);
 hipError_t launch_embed_key_ragged_fixup(const RaggedKeyArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
@@ -66,9 +68,9 @@ hipError_t launch_embed_ragged_fixup(const RaggedArgs &r, const uint32_t *list, 
 hipError_t launch_extract_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
                                        hipStream_t st);
 hipError_t launch_sigma1_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
-                                      hipStream_t st);
+                                      hipStream_t st, int px = 3);
 hipError_t launch_extract_keyed_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
-                                             hipStream_t st);
+                                             hipStream_t st, int px = 3);
 // the eight launchers per block size B: defined and instantiated for B = TMF_B in the size's own
 // translation units (tmfwm_ragged_strip.hip, tmfwm_ragged_fixup.hip), which alone see the kernels
 template <int B>
@@ -84,14 +86,15 @@ hipError_t embed_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const
 template <int B>
 hipError_t extract_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
 template <int B>
-hipError_t sigma1_map_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st);
+hipError_t sigma1_map_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st, int px);
 template <int B>
-hipError_t extract_keyed_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st);
+hipError_t extract_keyed_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st, int px);
 template <int B>
-hipError_t sigma1_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
+hipError_t sigma1_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st,
+                                 int px);
 template <int B>
 hipError_t extract_keyed_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
-                                        hipStream_t st);
+                                        hipStream_t st, int px);
 
 #if defined(__HIPCC__)
 // The table through the constant address space: a load from it at a wave-uniform address is a

@@ -37,16 +37,16 @@ hipError_t launch_extract_ragged(const RaggedArgs &r, int64_t waves, hipStream_t
     return for_block(r.block, [&](auto b) { return extract_ragged_b<b()>(r, (unsigned)waves, st); });
 }
 
-hipError_t launch_sigma1_map_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st)
+hipError_t launch_sigma1_map_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st, int px)
 {
-    if (waves <= 0 || waves > kGridMax) return hipErrorInvalidValue;
-    return for_block(r.block, [&](auto b) { return sigma1_map_ragged_b<b()>(r, (unsigned)waves, st); });
+    if (waves <= 0 || waves > kGridMax || (px != 3 && px != 4)) return hipErrorInvalidValue;
+    return for_block(r.block, [&](auto b) { return sigma1_map_ragged_b<b()>(r, (unsigned)waves, st, px); });
 }
 
-hipError_t launch_extract_keyed_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st)
+hipError_t launch_extract_keyed_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st, int px)
 {
-    if (waves <= 0 || waves > kGridMax) return hipErrorInvalidValue;
-    return for_block(r.block, [&](auto b) { return extract_keyed_ragged_b<b()>(r, (unsigned)waves, st); });
+    if (waves <= 0 || waves > kGridMax || (px != 3 && px != 4)) return hipErrorInvalidValue;
+    return for_block(r.block, [&](auto b) { return extract_keyed_ragged_b<b()>(r, (unsigned)waves, st, px); });
 }
 
 hipError_t launch_embed_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
@@ -62,15 +62,17 @@ hipError_t launch_extract_ragged_fixup(const RaggedArgs &r, const uint32_t *list
 }
 
 hipError_t launch_sigma1_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
-                                      hipStream_t st)
+                                      hipStream_t st, int px)
 {
-    return for_block(r.block, [&](auto b) { return sigma1_ragged_fixup_b<b()>(r, list, count, max_entries, st); });
+    if (px != 3 && px != 4) return hipErrorInvalidValue;
+    return for_block(r.block, [&](auto b) { return sigma1_ragged_fixup_b<b()>(r, list, count, max_entries, st, px); });
 }
 
 hipError_t launch_extract_keyed_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
-                                             hipStream_t st)
+                                             hipStream_t st, int px)
 {
-    return for_block(r.block, [&](auto b) { return extract_keyed_ragged_fixup_b<b()>(r, list, count, max_entries, st); });
+    if (px != 3 && px != 4) return hipErrorInvalidValue;
+    return for_block(r.block, [&](auto b) { return extract_keyed_ragged_fixup_b<b()>(r, list, count, max_entries, st, px); });
 }
 
 // The edge pixels of every frame of the chunk on one flat index over the table's edge prefix;

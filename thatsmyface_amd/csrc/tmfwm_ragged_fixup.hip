@@ -73,13 +73,13 @@ __global__ __launch_bounds__(64) void extract_ragged_fixup_kernel(RaggedArgs r, 
 }
 
 // keyed extraction (tmfwm_keyed.h): keyed_fix_block on the frame's one image
-template <int B, bool MAP>
+template <int B, bool MAP, int PX = 3>
 TMF_DEVI void keyed_ragged_fixup(const RaggedArgs &r, const uint32_t *__restrict__ list, const uint32_t *__restrict__ count)
 {
     fixup_walk<B, FixLdsS<B>>(list, count, [&](auto par, uint32_t id, FixLdsS<B> &f, int gl) {
         const RaggedFrame *fr = ragged_block_frame(r, id);
         const KeyedArgs a = ragged_keyed_view(r, fr);
-        keyed_fix_block<B, typename decltype(par)::Par, decltype(par)::G, MAP>(a, id - fr->block0, f, gl);
+        keyed_fix_block<B, typename decltype(par)::Par, decltype(par)::G, MAP, PX>(a, id - fr->block0, f, gl);
     });
 }
 
@@ -102,17 +102,34 @@ __global__ __launch_bounds__(64, kKeyedFixWaves<B>) void extract_keyed_ragged_fi
     keyed_ragged_fixup<B, false>(r, list, count);
 }
 
+// frames of 4-byte pixels (tmfwm_ragged_strip.hip): kernels of their own beside the 3-byte ones
 template <int B>
-hipError_t sigma1_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st)
+__global__ __launch_bounds__(64) void sigma1_ragged_fixup_px4_kernel(RaggedArgs r, const uint32_t *__restrict__ list,
+                                                                     const uint32_t *__restrict__ count)
 {
-    return launch_fixup<B>(sigma1_ragged_fixup_kernel<B>, r, list, count, max_entries, st);
+    keyed_ragged_fixup<B, true, 4>(r, list, count);
+}
+
+template <int B>
+__global__ __launch_bounds__(64, kKeyedFixWaves<B>) void extract_keyed_ragged_fixup_px4_kernel(RaggedArgs r, const uint32_t *__restrict__ list,
+                                                                            const uint32_t *__restrict__ count)
+{
+    keyed_ragged_fixup<B, false, 4>(r, list, count);
+}
+
+template <int B>
+hipError_t sigma1_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st,
+                                 int px)
+{
+    return launch_fixup<B>(px == 4 ? sigma1_ragged_fixup_px4_kernel<B> : sigma1_ragged_fixup_kernel<B>, r, list, count, max_entries, st);
 }
 
 template <int B>
 hipError_t extract_keyed_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
-                                        hipStream_t st)
+                                        hipStream_t st, int px)
 {
-    return launch_fixup<B>(extract_keyed_ragged_fixup_kernel<B>, r, list, count, max_entries, st);
+    return launch_fixup<B>(px == 4 ? extract_keyed_ragged_fixup_px4_kernel<B> : extract_keyed_ragged_fixup_kernel<B>, r, list, count,
+                           max_entries, st);
 }
 
 template <int B>
@@ -136,7 +153,7 @@ hipError_t extract_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, con
 template hipError_t embed_ragged_fixup_b<TMF_B>(const RaggedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
 template hipError_t embed_key_ragged_fixup_b<TMF_B>(const RaggedKeyArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
 template hipError_t extract_ragged_fixup_b<TMF_B>(const RaggedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
-template hipError_t sigma1_ragged_fixup_b<TMF_B>(const RaggedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
-template hipError_t extract_keyed_ragged_fixup_b<TMF_B>(const RaggedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t);
+template hipError_t sigma1_ragged_fixup_b<TMF_B>(const RaggedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t, int);
+template hipError_t extract_keyed_ragged_fixup_b<TMF_B>(const RaggedArgs &, const uint32_t *, const uint32_t *, int64_t, hipStream_t, int);
 
 }  // namespace tmf

@@ -123,7 +123,7 @@ template hipError_t extract_ragged_b<TMF_B>(const RaggedArgs &, unsigned, hipStr
 #if TMF_RAGGED_PART & 2
 // keyed extraction (tmfwm_keyed.h): keyed_sigma on the frame's one image; an undecided block goes
 // straight to the dgesdd route, a decided one through keyed_store on the one-frame view
-template <int B, bool MAP>
+template <int B, bool MAP, int PX = 3>
 TMF_DEVI void keyed_ragged_strip(const RaggedArgs &r)
 {
     constexpr int L = Geo<B>::L, BPW = Geo<B>::BPW, LD = B + 1;
@@ -135,7 +135,7 @@ TMF_DEVI void keyed_ragged_strip(const RaggedArgs &r)
     const StripPos pos = ragged_strip_pos<B>(f, id);
     float s;
     bool ok;
-    keyed_sigma<B, kPowerIters>(a, pos, lds + g * B * LD, q, s, ok);
+    keyed_sigma<B, kPowerIters, PX>(a, pos, lds + g * B * LD, q, s, ok);
     if (!pos.valid || q != 0) return;
     if (!ok) {
         a.fb_list[atomicAdd(a.fb_count, 1u)] = id;
@@ -156,22 +156,35 @@ __global__ __launch_bounds__(64, kKeyedWaves<B>) void extract_keyed_ragged_kerne
     keyed_ragged_strip<B, false>(r);
 }
 
+// frames of 4-byte pixels (R G B pad), read in place: kernels of their own beside the 3-byte ones
 template <int B>
-hipError_t sigma1_map_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st)
+__global__ __launch_bounds__(64, kKeyedWaves<B>) void sigma1_map_ragged_px4_kernel(RaggedArgs r)
 {
-    hipLaunchKernelGGL((sigma1_map_ragged_kernel<B>), dim3(waves), dim3(64), 0, st, r);
+    keyed_ragged_strip<B, true, 4>(r);
+}
+
+template <int B>
+__global__ __launch_bounds__(64, kKeyedWaves<B>) void extract_keyed_ragged_px4_kernel(RaggedArgs r)
+{
+    keyed_ragged_strip<B, false, 4>(r);
+}
+
+template <int B>
+hipError_t sigma1_map_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st, int px)
+{
+    hipLaunchKernelGGL((px == 4 ? sigma1_map_ragged_px4_kernel<B> : sigma1_map_ragged_kernel<B>), dim3(waves), dim3(64), 0, st, r);
     return hipGetLastError();
 }
 
 template <int B>
-hipError_t extract_keyed_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st)
+hipError_t extract_keyed_ragged_b(const RaggedArgs &r, unsigned waves, hipStream_t st, int px)
 {
-    hipLaunchKernelGGL((extract_keyed_ragged_kernel<B>), dim3(waves), dim3(64), 0, st, r);
+    hipLaunchKernelGGL((px == 4 ? extract_keyed_ragged_px4_kernel<B> : extract_keyed_ragged_kernel<B>), dim3(waves), dim3(64), 0, st, r);
     return hipGetLastError();
 }
 
-template hipError_t sigma1_map_ragged_b<TMF_B>(const RaggedArgs &, unsigned, hipStream_t);
-template hipError_t extract_keyed_ragged_b<TMF_B>(const RaggedArgs &, unsigned, hipStream_t);
+template hipError_t sigma1_map_ragged_b<TMF_B>(const RaggedArgs &, unsigned, hipStream_t, int);
+template hipError_t extract_keyed_ragged_b<TMF_B>(const RaggedArgs &, unsigned, hipStream_t, int);
 #endif
 
 }  // namespace tmf

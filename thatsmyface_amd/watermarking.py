@@ -409,23 +409,37 @@ def _block_size(custom_settings):
     return block_size, alpha
 
 
+def _read_pixels(image):
+    """(address, pixel bytes, keepalive) of an RGB image's pixels for a call that only reads them:
+    PIL's own 4-byte memory where the zero-copy path can hand it over (_rgbx_view), else a
+    contiguous 3-byte copy (no pyarrow, a read-only image, an image in several memory blocks)."""
+    view = _rgbx_view(image) if _arrow() is not None and image.width > 0 and image.height > 0 else None
+    if view is not None:
+        return view[0], _lib.PIX_RGBX, view[1]
+    arr = np.ascontiguousarray(np.asarray(image, dtype=np.uint8))
+    return _ptr(arr), _lib.PIX_RGB, arr
+
+
 def extraction_key(original_image, custom_settings=None) -> np.ndarray:
     """All that extract_watermark uses of the original image (:279-285): float32 (H//b, W//b),
     f32(sigma_1) of each block's DCT.  Store it (np.save) instead of the original and extract
-    with extract_watermark_keyed.  A key belongs to one block size and one image size."""
+    with extract_watermark_keyed.  A key belongs to one block size and one image size.  The
+    library reads PIL's own pixels where they lie (tmfwm_sigma1_map_px), as embed_watermark does."""
     block_size, _ = _block_size(custom_settings)
-    o = np.ascontiguousarray(np.asarray(_rgb_image(original_image), dtype=np.uint8))
-    height, width = o.shape[:2]
+    image = _rgb_image(original_image)
+    width, height = image.size
     nbh, nbw = height // block_size, width // block_size
     key = np.empty((nbh, nbw), np.float32)
     if nbh == 0 or nbw == 0:
         return key
+    src, px, keep = _read_pixels(image)
     L = _lib.load()
     _lib.check(
-        L.tmfwm_sigma1_map(_ptr(o), 1, height, width, o.size, block_size, _ptr(key), _lib.MEM_HOST, None, _route(custom_settings),
-                           None),
+        L.tmfwm_sigma1_map_px(src, px, height * width * px, 1, height, width, block_size, _ptr(key), _lib.MEM_HOST, None,
+                              _route(custom_settings), None),
         "extraction_key",
     )
+    del keep
     return key
 
 
@@ -433,18 +447,36 @@ def embed_watermark_with_key(image, watermark_data, preserve_ratio=False, custom
     """embed_watermark and extraction_key(image) in one call and one upload (tmfwm_embed_key):
     (the watermarked RGB image, the float32 (H//b, W//b) key of `image`).  The image is
     embed_watermark's pixel for pixel, the key extraction_key's bit for bit: what
-    extract_watermark_keyed takes with the watermarked image.  3-byte pixels on both sides."""
+    extract_watermark_keyed takes with the watermarked image.  PIL's own 4-byte pixels go in and
+    come out where the zero-copy path can run (tmfwm_embed_key_px), as in embed_watermark; the
+    copying path otherwise."""
     block_size, alpha = _block_size(custom_settings)
-    rgb = np.ascontiguousarray(np.asarray(_rgb_image(image), dtype=np.uint8))
-    height, width = rgb.shape[:2]
+    image = _rgb_image(image)
+    width, height = image.size
     nbh, nbw = height // block_size, width // block_size
     tile = _tile_for(watermark_data, nbh, nbw, preserve_ratio)
-    out = np.empty_like(rgb)
     key = np.empty((nbh, nbw), np.float32)
+    route = _route(custom_settings)
     L = _lib.load()
+    if _arrow() is not None and height > 0 and width > 0:
+        src, src_px, keep = _read_pixels(image)
+        out = _take_out(height * width * 4)
+        try:
+            _lib.check(
+                L.tmfwm_embed_key_px(src, src_px, height * width * src_px, 1, height, width, _ptr(tile), 0, block_size, float(alpha),
+                                     _ptr(out), _lib.PIX_RGBX, height * width * 4, _ptr(key), 0, _lib.MEM_HOST, None, route, None),
+                "embed_watermark_with_key",
+            )
+        except BaseException:
+            _give_back(out)
+            raise
+        del keep
+        return _rgb_from_rgbx(out, width, height), key
+    rgb = np.ascontiguousarray(np.asarray(image, dtype=np.uint8))
+    out = np.empty_like(rgb)
     _lib.check(
         L.tmfwm_embed_key(_ptr(rgb), 1, height, width, rgb.size, _ptr(tile), 0, block_size, float(alpha), _ptr(out), _ptr(key), 0,
-                          _lib.MEM_HOST, None, _route(custom_settings), None),
+                          _lib.MEM_HOST, None, route, None),
         "embed_watermark_with_key",
     )
     return Image.fromarray(out), key
@@ -456,8 +488,8 @@ def extract_watermark_keyed(watermarked_image, key, custom_settings=None):
     block_size, alpha = _block_size(custom_settings)
     if not isinstance(key, np.ndarray) or key.dtype != np.float32:
         raise TypeError(f"key must be a float32 numpy array (extraction_key's result), got {getattr(key, 'dtype', type(key))}")
-    w = np.ascontiguousarray(np.asarray(_rgb_image(watermarked_image), dtype=np.uint8))
-    height, width = w.shape[:2]
+    image = _rgb_image(watermarked_image)
+    width, height = image.size
     nbh, nbw = height // block_size, width // block_size
     if key.shape != (nbh, nbw):
         raise ValueError(
@@ -468,10 +500,12 @@ def extract_watermark_keyed(watermarked_image, key, custom_settings=None):
         return Image.fromarray(np.zeros((nbh, nbw), np.uint8))
     key = np.ascontiguousarray(key)
     out = np.empty((nbh, nbw), np.uint8)
+    src, px, keep = _read_pixels(image)
     L = _lib.load()
     _lib.check(
-        L.tmfwm_extract_keyed(_ptr(w), 1, height, width, w.size, _ptr(key), 0, block_size, float(alpha), _ptr(out), _lib.MEM_HOST,
-                              None, _route(custom_settings), None),
+        L.tmfwm_extract_keyed_px(src, px, height * width * px, 1, height, width, _ptr(key), 0, block_size, float(alpha), _ptr(out),
+                                 _lib.MEM_HOST, None, _route(custom_settings), None),
         "extract_watermark_keyed",
     )
+    del keep
     return Image.fromarray(out)

@@ -70,10 +70,19 @@ def main():
     wm_dec = Image.open(io.BytesIO(b2.getvalue()))
     wm_dec.load()
     out["extract_watermark_decoded_ms"] = timed(lambda: W.extract_watermark(wm_dec, cover, cs))
+    # the keyed drop-ins (a verifier that stores keys instead of originals): the key of an upload, the
+    # enrolment call, the keyed extract of a decoded upload
+    key = W.extraction_key(cover, cs)
+    out["extraction_key_ms"] = timed(lambda: W.extraction_key(cover, cs))
+    out["embed_watermark_with_key_ms"] = timed(lambda: W.embed_watermark_with_key(cover, png, True, cs))
+    out["extract_watermark_keyed_ms"] = timed(lambda: W.extract_watermark_keyed(wm_dec, key, cs))
     # the copying path (np.asarray in, Image.fromarray out), for comparison
     W._zero_copy = False
     out["embed_watermark_copying_path_ms"] = timed(lambda: W.embed_watermark(cover, png, True, cs))
     out["extract_watermark_copying_path_ms"] = timed(lambda: W.extract_watermark(wm_dec, cover, cs))
+    out["extraction_key_copying_path_ms"] = timed(lambda: W.extraction_key(cover, cs))
+    out["embed_watermark_with_key_copying_path_ms"] = timed(lambda: W.embed_watermark_with_key(cover, png, True, cs))
+    out["extract_watermark_keyed_copying_path_ms"] = timed(lambda: W.extract_watermark_keyed(wm_dec, key, cs))
     W._zero_copy = True
     # where embed_watermark's time goes (its stages, each timed alone)
     from thatsmyface_amd import _lib

@@ -8,6 +8,12 @@ One process, HIP events, the variants alternating round by round on the same fra
 Before timing, the keyed bytes are compared with the pair path's.  Prints one JSON line per
 (block, kind): microseconds per frame (median, min, max over the rounds), the A/A spread, and
 the ratios keyed / pair and (map + keyed) / pair.
+
+--pixel-bytes 4 adds, in the same rounds, the two ways a holder of R G B pad frames has:
+  keyed4, map4            the same calls on the (N, H, W, 4) frames, read in place
+  keyed_pack, map_pack    frames[..., :3].contiguous() and then the 3-byte call (what such a holder
+                          had to do before the keyed calls took 4-byte frames)
+and their ratios (in place / 3-byte, in place / pack-then-call).
 """
 import argparse
 import json
@@ -33,6 +39,13 @@ def covers(kind, n, H, W, dev):
     return torch.cat([photo_covers(min(16, n - i), H, W, 5 + i, dev) for i in range(0, n, 16)])
 
 
+def rgbx(frames):
+    """(N, H, W, 3) -> (N, H, W, 4): the same R, G, B and a pad byte of 255"""
+    out = torch.full(frames.shape[:3] + (4,), 255, dtype=torch.uint8, device=frames.device)
+    out[..., :3] = frames
+    return out
+
+
 def timed(fn, reps):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
@@ -53,6 +66,7 @@ def main():
     p.add_argument("--rounds", type=int, default=7)
     p.add_argument("--reps", type=int, default=3, help="calls per timed window")
     p.add_argument("--route", choices=["hybrid", "reference", "rank1", "rank1_reference"], default="hybrid")
+    p.add_argument("--pixel-bytes", type=int, choices=[3, 4], default=3, help="4: also time the keyed calls on R G B pad frames")
     p.add_argument("--out", help="also append the JSON lines to this file")
     a = p.parse_args()
     if not torch.cuda.is_available():
@@ -75,6 +89,18 @@ def main():
                 "map": lambda: batch.sigma1_map(o, b, out=key, route=rt),
                 "pair_b": lambda: batch.extract_batch(w, o, b, 0.1, out=ext_p, route=rt),
             }
+            if a.pixel_bytes == 4:
+                o4, w4 = rgbx(o), rgbx(w)
+                key4, ext4 = torch.empty_like(key), torch.empty_like(ext_k)
+                batch.sigma1_map(o4, b, out=key4, route=rt)
+                batch.extract_keyed(w4, key, b, 0.1, out=ext4, route=rt)
+                same = same and bool(torch.equal(ext4, ext_k)) and bool(torch.equal(key4.view(torch.int32), key.view(torch.int32)))
+                variants.update({
+                    "keyed4": lambda: batch.extract_keyed(w4, key, b, 0.1, out=ext4, route=rt),
+                    "map4": lambda: batch.sigma1_map(o4, b, out=key4, route=rt),
+                    "keyed_pack": lambda: batch.extract_keyed(w4[..., :3].contiguous(), key, b, 0.1, out=ext4, route=rt),
+                    "map_pack": lambda: batch.sigma1_map(o4[..., :3].contiguous(), b, out=key4, route=rt),
+                })
             for fn in variants.values():  # warm-up: every timed shape once more
                 fn()
             torch.cuda.synchronize()
@@ -95,6 +121,13 @@ def main():
                 "dgesdd_route_blocks": {"pair": sp["lapack_blocks"], "keyed": sk["lapack_blocks"], "map": sm["lapack_blocks"]},
                 "list_pass_blocks": {"pair": sp["list_pass_blocks"], "keyed": sk["list_pass_blocks"], "map": sm["list_pass_blocks"]},
             }
+            if a.pixel_bytes == 4:
+                line["keyed_round_spread"] = round((max(t["keyed"]) - min(t["keyed"])) / med["keyed"], 4)
+                line["map_round_spread"] = round((max(t["map"]) - min(t["map"])) / med["map"], 4)
+                for k in ("keyed", "map"):
+                    line[k + "4_over_" + k] = round(med[k + "4"] / med[k], 4)
+                    line[k + "4_over_" + k + "_pack"] = round(med[k + "4"] / med[k + "_pack"], 4)
+                del o4, w4, key4, ext4
             s = json.dumps(line)
             print(s, flush=True)
             if a.out:
