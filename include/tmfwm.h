@@ -277,8 +277,9 @@ typedef struct {
  * TMFWM_MEM_DEVICE: asynchronous on `hip_stream` unless n_lapack_blocks is given; every `out`
  * must be disjoint from every `rgb` and `wm_tile` of the call and from every other `out`
  * (TMFWM_ERR_INVALID otherwise; inputs may share memory).  Routes: TMFWM_ROUTE_HYBRID and
- * TMFWM_ROUTE_REFERENCE; the ragged calls do not take the rank-1 routes yet
- * (TMFWM_ROUTE_RANK1 and TMFWM_ROUTE_RANK1_REFERENCE return TMFWM_ERR_UNSUPPORTED).
+ * TMFWM_ROUTE_REFERENCE; this call and the other ragged calls here do not take the rank-1 routes
+ * (TMFWM_ROUTE_RANK1 and TMFWM_ROUTE_RANK1_REFERENCE return TMFWM_ERR_UNSUPPORTED;
+ * tmfwm_embed_ragged_rank1 and tmfwm_embed_key_ragged_rank1 below do).
  * *n_lapack_blocks (optional) receives the dgesdd-route blocks of all frames together; a dbdsqr
  * that does not converge fails a synchronising call as it does tmfwm_embed_ex.  The strip pass
  * runs every block to the end (no list pass): tmfwm_last_list_pass_blocks() reports 0.
@@ -417,6 +418,34 @@ typedef struct {
 } tmfwm_embed_key_frame;     /* 40 bytes */
 int tmfwm_embed_key_ragged(const tmfwm_embed_key_frame *frames, int64_t n_frames, int32_t block, double alpha,
                            int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
+
+/*
+ * The ragged embed on every route (added within ABI 10; the version number is unchanged, and
+ * tmfwm_embed_ragged / tmfwm_embed_key_ragged keep refusing the rank-1 routes).  Descriptors,
+ * memory kinds, the overlap checks, frames without a block, zero-area frames, the count, the
+ * non-convergence report and "all arguments checked before the device is touched" are
+ * tmfwm_embed_ragged's.  TMFWM_ROUTE_HYBRID and TMFWM_ROUTE_REFERENCE are that call, unchanged.
+ * TMFWM_ROUTE_RANK1 and TMFWM_ROUTE_RANK1_REFERENCE run the rank-1 pre-pass over every frame's
+ * blocks in one launch (any block size 4..16 even); the blocks it leaves go to one list pass on
+ * the hybrid route (TMFWM_ROUTE_RANK1) or straight to the dgesdd route
+ * (TMFWM_ROUTE_RANK1_REFERENCE).  Frame i's bytes are tmfwm_embed_route's on that frame alone on
+ * the same route -- the reference route's on every route.  *n_lapack_blocks is the sum over the
+ * frames, and tmfwm_last_list_pass_blocks() reports what the pre-pass left to the list pass on
+ * TMFWM_ROUTE_RANK1.
+ */
+int tmfwm_embed_ragged_rank1(const tmfwm_embed_frame *frames, int64_t n_frames, int32_t block, double alpha, int32_t mem_kind,
+                             void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
+
+/*
+ * tmfwm_embed_key_ragged on every route.  TMFWM_ROUTE_HYBRID and TMFWM_ROUTE_REFERENCE are that
+ * call, unchanged.  On the rank-1 routes the call is composed, as tmfwm_embed_key is there:
+ * tmfwm_embed_ragged_rank1's passes, then tmfwm_sigma1_map_ragged's on the same stream over the
+ * same buffers (TMFWM_MEM_HOST: over the one staged copy).  Frame i's `out` bytes are
+ * tmfwm_embed_ragged_rank1's, its key bits tmfwm_sigma1_map_ragged's, and the counts are the sums
+ * over both.
+ */
+int tmfwm_embed_key_ragged_rank1(const tmfwm_embed_key_frame *frames, int64_t n_frames, int32_t block, double alpha,
+                                 int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
 
 /* tmfwm_extract_route with a pixel layout and frame stride per input image (ABI 8). */
 int tmfwm_extract_px(const uint8_t *wm_rgb, int32_t wm_pixel_bytes, int64_t wm_frame_stride, const uint8_t *orig_rgb,

@@ -124,6 +124,8 @@ SIGNATURES = {
     "tmfwm_extract_keyed_ragged": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _VP, _I32, _VP]),
     "tmfwm_embed_key": (ctypes.c_int, [_VP, _I64, _I32, _I32, _I64, _VP, _I64, _I32, _D, _VP, _VP, _I64, _I32, _VP, _I32, _VP]),
     "tmfwm_embed_key_ragged": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _VP, _I32, _VP]),
+    "tmfwm_embed_ragged_rank1": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _VP, _I32, _VP]),
+    "tmfwm_embed_key_ragged_rank1": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _VP, _I32, _VP]),
     # the keyed calls with a pixel layout (3 or 4 bytes per pixel)
     "tmfwm_sigma1_map_px": (ctypes.c_int, [_VP, _I32, _I64, _I64, _I32, _I32, _I32, _VP, _I32, _VP, _I32, _VP]),
     "tmfwm_extract_keyed_px": (ctypes.c_int, [_VP, _I32, _I64, _I64, _I32, _I32, _VP, _I64, _I32, _D, _VP, _I32, _VP, _I32, _VP]),

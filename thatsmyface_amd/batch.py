@@ -260,11 +260,11 @@ def _ragged_route(route) -> int:
     return code
 
 
-def _embed_ragged_args(frames, tiles, block, route, out):
+def _embed_ragged_args(frames, tiles, block, route, out, rank1_routes: bool = False):
     """embed_ragged's checks and output views: (frames, tiles, out, device, route code)."""
     if block not in SUPPORTED_BLOCK_SIZES:
         raise NotImplementedError(f"block {block}")
-    code = _ragged_route(route)
+    code = _lib.route_code(route) if rank1_routes else _ragged_route(route)
     frames, dev = _check_ragged(frames, "frames")
     tiles = list(tiles)
     if len(tiles) != len(frames):
@@ -281,6 +281,32 @@ def _embed_ragged_args(frames, tiles, block, route, out):
         if len(out) != len(frames) or any(o.shape != f.shape for o, f in zip(out, frames)):
             raise ValueError("out must hold one tensor per frame, shaped like it")
     return frames, tiles, out, dev, code
+
+
+def embed_ragged_rank1(frames, tiles, block: int = 8, alpha: float = 0.1, out=None, stream=None, stats: dict | None = None,
+                       route: str = "rank1") -> list:
+    """embed_ragged on every route (tmfwm_embed_ragged_rank1): "rank1" and "rank1_reference" run the
+    rank-1 pre-pass over all the frames' blocks in one launch, and what it leaves goes to one list
+    pass on the hybrid route ("rank1") or straight to the dgesdd route ("rank1_reference");
+    "hybrid" and "reference" are embed_ragged itself.  Arguments, checks and the return value are
+    embed_ragged's; output i is the bytes of embed_batch(frames[i][None], tiles[i], ..., route=route)[0].
+    stats["list_pass_blocks"] is what the pre-pass left to the list pass on "rank1"."""
+    import ctypes
+
+    frames, tiles, out, dev, code = _embed_ragged_args(frames, tiles, block, route, out, rank1_routes=True)
+    desc = (_lib.EmbedFrame * max(len(frames), 1))()
+    for i, (f, t, o) in enumerate(zip(frames, tiles, out)):
+        desc[i] = _lib.EmbedFrame(f.data_ptr(), o.data_ptr(), t.data_ptr(), f.shape[0], f.shape[1])
+    cnt, ptr = _count_ptr(stats)
+    L = _lib.load()
+    if frames:
+        with torch.cuda.device(dev):
+            _lib.check(L.tmfwm_embed_ragged_rank1(ctypes.addressof(desc), len(frames), block, float(alpha), _lib.MEM_DEVICE,
+                                                  _stream(stream), code, ptr), "embed_ragged_rank1")
+    if stats is not None:
+        stats["lapack_blocks"] = int(cnt.value)
+        stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks()) if frames else 0
+    return list(out)
 
 
 def embed_ragged(frames, tiles, block: int = 8, alpha: float = 0.1, out=None, stream=None, stats: dict | None = None,
@@ -429,6 +455,36 @@ def embed_with_key_ragged(frames, tiles, block: int = 8, alpha: float = 0.1, out
         with torch.cuda.device(dev):
             _lib.check(L.tmfwm_embed_key_ragged(ctypes.addressof(desc), len(frames), block, float(alpha), _lib.MEM_DEVICE,
                                                 _stream(stream), code, ptr), "embed_with_key_ragged")
+    if stats is not None:
+        stats["lapack_blocks"] = int(cnt.value)
+        stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks()) if frames else 0
+    return list(out), list(keys)
+
+
+def embed_with_key_ragged_rank1(frames, tiles, block: int = 8, alpha: float = 0.1, out=None, key_out=None, stream=None,
+                                stats: dict | None = None, route: str = "rank1"):
+    """embed_with_key_ragged on every route (tmfwm_embed_key_ragged_rank1): on "rank1" and
+    "rank1_reference" embed_ragged_rank1's passes and then sigma1_map_ragged's in the one call
+    (the counts are the sums over both); "hybrid" and "reference" are embed_with_key_ragged itself.
+    Arguments, checks and the return value are embed_with_key_ragged's."""
+    import ctypes
+
+    frames, tiles, out, dev, code = _embed_ragged_args(frames, tiles, block, route, out, rank1_routes=True)
+    shapes = [(f.shape[0] // block, f.shape[1] // block) for f in frames]
+    if key_out is None:  # float32 views of one uint8 allocation: its pieces start on 16-byte boundaries
+        keys = [v.view(torch.float32).view(shapes[i]) for i, v in enumerate(
+            _ragged_views([4 * a * b for a, b in shapes], lambda i: (4 * shapes[i][0] * shapes[i][1],), dev))] if frames else []
+    else:
+        keys = _check_ragged_out(key_out, shapes, torch.float32, dev, "key")
+    desc = (_lib.EmbedKeyFrame * max(len(frames), 1))()
+    for i, (f, t, o, k) in enumerate(zip(frames, tiles, out, keys)):
+        desc[i] = _lib.EmbedKeyFrame(f.data_ptr(), o.data_ptr(), t.data_ptr(), k.data_ptr(), f.shape[0], f.shape[1])
+    cnt, ptr = _count_ptr(stats)
+    L = _lib.load()
+    if frames:
+        with torch.cuda.device(dev):
+            _lib.check(L.tmfwm_embed_key_ragged_rank1(ctypes.addressof(desc), len(frames), block, float(alpha), _lib.MEM_DEVICE,
+                                                      _stream(stream), code, ptr), "embed_with_key_ragged_rank1")
     if stats is not None:
         stats["lapack_blocks"] = int(cnt.value)
         stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks()) if frames else 0

@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -1585,10 +1586,11 @@ const char *const kRaggedNames[5][3] = {{"rgb", "wm_tile", "out"}, {"wm_rgb", "o
 
 // the checks every ragged call makes before it touches the device
 int check_ragged_call(const void *frames, int64_t n, int32_t block, double alpha, RKind kind, int32_t mem_kind, int32_t route,
-                      int64_t *n_lapack)
+                      int64_t *n_lapack, bool rank1_routes = false)
 {
     const bool extract = kind == RKind::Extract || kind == RKind::Keyed;
-    if (int rc = begin_call(route, n_lapack, false)) return rc;  // no rank-1 routes yet; no list pass in a ragged call
+    // the rank-1 routes: tmfwm_embed_ragged_rank1 / tmfwm_embed_key_ragged_rank1 alone (the one ragged list pass)
+    if (int rc = begin_call(route, n_lapack, rank1_routes)) return rc;
     if (n < 0) return fail(TMFWM_ERR_INVALID, "negative size (n=%lld)", (long long)n);
     if (n > 0 && !frames) return fail(TMFWM_ERR_INVALID, "frames is NULL");
     if (!supported_block(block)) return fail(TMFWM_ERR_UNSUPPORTED, "block size %d not supported (even, 4..16)", block);
@@ -1734,14 +1736,33 @@ void give_table(TableSlot &s, hipStream_t st)
 // enough edge pixels for one launch of the edge pass.
 struct RaggedChunk {
     int64_t first = 0, n = 0, waves = 0, blocks = 0, edge = 0;
+    int64_t with_blocks = 0;  // frames that have a block
+    uint32_t shards = 0;      // TMFWM_ROUTE_RANK1: the list-pass shards the chunk uses
 };
 constexpr int64_t kEdgeCap = int64_t(1) << 38;
 
-// the frame table of the frames that have work, with chunk-relative prefixes, and the chunks
-// (RKind::EmbedKey: `keys` receives the table's side table, each entry's key output)
-void plan_ragged(const std::vector<RFrame> &fr, int32_t block, RKind kind, std::vector<tmf::RaggedFrame> &table,
-                 std::vector<RaggedChunk> &chunks, std::vector<float *> &keys)
+bool rank1_route(int route) { return route == TMFWM_ROUTE_RANK1 || route == TMFWM_ROUTE_RANK1_REFERENCE; }
+
+// What run_ragged takes: the frame table of the frames that have work, with chunk-relative
+// prefixes, the chunks, and the table's side tables -- RKind::EmbedKey: each entry's key output;
+// TMFWM_ROUTE_RANK1: each entry's list-pass shards, relative to its chunk as the ids are.
+struct RaggedPlan {
+    RKind kind;
+    int route;
+    std::vector<tmf::RaggedFrame> table;
+    std::vector<RaggedChunk> chunks;
+    std::vector<float *> keys;
+    std::vector<tmf::RaggedShards> shards;
+};
+
+void plan_ragged(const std::vector<RFrame> &fr, int32_t block, RKind kind, int route, RaggedPlan &plan)
 {
+    plan.kind = kind;
+    plan.route = route;
+    std::vector<tmf::RaggedFrame> &table = plan.table;
+    std::vector<RaggedChunk> &chunks = plan.chunks;
+    std::vector<float *> &keys = plan.keys;
+    const bool list_pass = route == TMFWM_ROUTE_RANK1;
     const int bpw = tmf::ragged_strip_blocks(block);
     const int64_t cap = list_cap();
     RaggedChunk c;
@@ -1761,7 +1782,8 @@ void plan_ragged(const std::vector<RFrame> &fr, int32_t block, RKind kind, std::
         const int64_t waves = (int64_t)t.nbh * t.strips_per_row, blocks = (int64_t)t.nbh * t.nbw;
         const int64_t edge = embeds(kind) ? (int64_t)f.H * f.W - blocks * block * block : 0;
         if (blocks == 0 && edge == 0) continue;
-        if (c.n > 0 && (c.blocks + blocks > cap || c.edge + edge > kEdgeCap)) {
+        if (c.n > 0 && (c.blocks + blocks > cap || c.edge + edge > kEdgeCap ||
+                        (list_pass && blocks > 0 && tmf::ragged_shards_full(c.with_blocks)))) {
             chunks.push_back(c);
             c = RaggedChunk{};
             c.first = (int64_t)table.size();
@@ -1772,27 +1794,42 @@ void plan_ragged(const std::vector<RFrame> &fr, int32_t block, RKind kind, std::
         table.push_back(t);
         if (kind == RKind::EmbedKey) keys.push_back(reinterpret_cast<float *>(f.out2));
         ++c.n;
+        c.with_blocks += blocks > 0;
         c.waves += waves;
         c.blocks += blocks;
         c.edge += edge;
     }
     if (c.n > 0) chunks.push_back(c);
+    if (list_pass) {
+        plan.shards.resize(table.size());
+        for (RaggedChunk &k : chunks) k.shards = tmf::ragged_plan_shards(table.data() + k.first, k.n, plan.shards.data() + k.first);
+    }
 }
 
 // Both passes of a ragged call over device-resident frames: the frame table uploaded, then the
 // chunks through two_pass, with the edge pass between a chunk's first pass and its fixup pass and
 // neither of the two for a chunk without a block.
-int run_ragged(int32_t block, double alpha, RKind kind, hipStream_t st, int route, const Report &rep,
-               const std::vector<tmf::RaggedFrame> &table, const std::vector<RaggedChunk> &chunks, const std::vector<float *> &keys,
+int run_ragged(int32_t block, double alpha, hipStream_t st, const Report &rep, const RaggedPlan &plan,
                int px = 3)  // px: the keyed kinds' bytes per pixel
 {
+    const RKind kind = plan.kind;
+    const int route = plan.route;
+    const std::vector<tmf::RaggedFrame> &table = plan.table;
+    const std::vector<RaggedChunk> &chunks = plan.chunks;
+    const std::vector<float *> &keys = plan.keys;
     if (chunks.empty()) return 0;
-    // the frame table and behind it the key side table (RKind::EmbedKey; empty otherwise), one upload
-    const size_t fbytes = table.size() * sizeof(tmf::RaggedFrame), tbytes = fbytes + keys.size() * sizeof(float *);
+    // on a rank-1 route the strip launch is the pre-pass (the plain embed alone: the key call composes, ragged_call)
+    const bool pre = rank1_route(route) && kind == RKind::Embed && tmf::rank1_block(block);
+    const bool list_pass = pre && route == TMFWM_ROUTE_RANK1;
+    // the frame table and behind it the side tables -- the keys (RKind::EmbedKey), the list-pass
+    // shards (TMFWM_ROUTE_RANK1); empty otherwise -- in one upload
+    const size_t fbytes = table.size() * sizeof(tmf::RaggedFrame), kbytes = keys.size() * sizeof(float *);
+    const size_t tbytes = fbytes + kbytes + plan.shards.size() * sizeof(tmf::RaggedShards);
     TableSlot slot;
     if (int rc = take_table(tbytes, stream_device(st), slot)) return rc;
     std::copy(table.begin(), table.end(), static_cast<tmf::RaggedFrame *>(slot.p));
     std::copy(keys.begin(), keys.end(), reinterpret_cast<float **>(static_cast<uint8_t *>(slot.p) + fbytes));
+    std::copy(plan.shards.begin(), plan.shards.end(), reinterpret_cast<tmf::RaggedShards *>(static_cast<uint8_t *>(slot.p) + fbytes + kbytes));
     DevBuf dtable;
     int rc = dtable.alloc(tbytes, st, "frame table");
     if (rc == 0 && hipMemcpyAsync(dtable.p, slot.p, tbytes, hipMemcpyHostToDevice, st) != hipSuccess)
@@ -1801,8 +1838,29 @@ int run_ragged(int32_t block, double alpha, RKind kind, hipStream_t st, int rout
     if (rc) return rc;
     std::vector<int64_t> blocks;
     for (const RaggedChunk &k : chunks) blocks.push_back(k.blocks);
-    return two_pass(blocks, false, true, st, rep, [&](int64_t c, const ChunkLists &w) -> int {
+    return two_pass(blocks, list_pass, true, st, rep, [&](int64_t c, const ChunkLists &w) -> int {
         const RaggedChunk &k = chunks[(size_t)c];
+        if (pre) {  // the pre-pass (+ its list pass on TMFWM_ROUTE_RANK1), the edges, the dgesdd route
+            tmf::RaggedRank1Args r{};
+            r.frames = static_cast<const tmf::RaggedFrame *>(dtable.p) + k.first;
+            r.nframes = (int32_t)k.n;
+            r.block = block;
+            r.alpha = alpha;
+            r.alpha32 = (float)alpha;
+            r.fb_list = w.fb_list;
+            r.fb_count = w.fb_count;
+            r.fb_bad = w.fb_bad;
+            if (list_pass) {  // ids and shard ranges are relative to the chunk
+                r.shards = reinterpret_cast<const tmf::RaggedShards *>(static_cast<const uint8_t *>(dtable.p) + fbytes + kbytes) + k.first;
+                r.slow_list = w.slow_list;
+                r.slow_count = w.slow_count;
+                r.slow_shards = w.slow_shards;
+            }
+            if (k.blocks > 0) TMF_HIP(tmf::launch_embed_rank1_ragged(r, k.waves, k.shards, st));
+            TMF_HIP(tmf::launch_edges_ragged(r, k.edge, st));
+            if (k.blocks > 0) TMF_HIP(tmf::launch_embed_ragged_fixup(r, r.fb_list, r.fb_count, k.blocks, st));
+            return 0;
+        }
         tmf::RaggedKeyArgs r{};  // (the other kinds take its RaggedArgs part)
         r.frames = static_cast<const tmf::RaggedFrame *>(dtable.p) + k.first;
         r.nframes = (int32_t)k.n;
@@ -1843,14 +1901,44 @@ int ragged_call(std::vector<RFrame> &fr, int32_t block, double alpha, RKind kind
     if (int rc = need_device()) return rc;
     if (fr.empty()) return 0;
     hipStream_t st = pick_stream(hip_stream);
-    std::vector<tmf::RaggedFrame> table;
-    std::vector<RaggedChunk> chunks;
-    std::vector<float *> keys;
     const int px = fr[0].px;  // one layout per call
+    // The call's parts, each a plan of its own run through run_ragged on the one stream: one, or --
+    // the key call on a rank-1 route, composed as tmfwm_embed_key is (embed_key_composed: the
+    // pre-pass stores no key) -- the embed's passes and then tmfwm_sigma1_map_ragged's over the
+    // same buffers.  The call's counts are the sums over its parts.
+    const bool composed = kind == RKind::EmbedKey && tmf::embed_key_composed(block, route, true) && rank1_route(route);
+    struct Part {
+        RaggedPlan plan;
+        int64_t n = 0;
+    };
+    std::vector<Part> parts(composed ? 2 : 1);
+    auto plan_parts = [&](const std::vector<RFrame> &v) {
+        if (!composed) return plan_ragged(v, block, kind, route, parts[0].plan);
+        std::vector<RFrame> emb(v), map(v);
+        for (size_t i = 0; i < v.size(); ++i) {
+            emb[i].out2 = nullptr;
+            map[i].in1 = nullptr;
+            map[i].out = v[i].out2;
+            map[i].out2 = nullptr;
+        }
+        plan_ragged(emb, block, RKind::Embed, route, parts[0].plan);
+        plan_ragged(map, block, RKind::Map, TMFWM_ROUTE_HYBRID, parts[1].plan);
+    };
+    int64_t total_n = 0, total_list = 0;
     if (mem_kind == TMFWM_MEM_DEVICE) {
         if (int rc = check_ragged_device(fr, block, kind)) return rc;
-        plan_ragged(fr, block, kind, table, chunks, keys);
-        return run_ragged(block, alpha, kind, st, route, device_report(n_lapack), table, chunks, keys, px);
+        plan_parts(fr);
+        for (Part &p : parts) {
+            t_list_pass = 0;
+            if (int rc = run_ragged(block, alpha, st, device_report(n_lapack ? &p.n : nullptr), p.plan, px)) return rc;
+            total_n += p.n;
+            total_list += t_list_pass;
+        }
+        if (n_lapack) {
+            *n_lapack = total_n;
+            t_list_pass = total_list;
+        }
+        return 0;
     }
     // host memory: every buffer of the call in one device allocation (16-byte aligned pieces),
     // results copied back, one synchronisation
@@ -1879,16 +1967,28 @@ int ragged_call(std::vector<RFrame> &fr, int32_t block, double alpha, RKind kind
         TMF_HIP(hipMemcpyAsync(base + off[3 * i], fr[i].in0, (size_t)fr[i].pixel_bytes(), hipMemcpyHostToDevice, st));
         if (ib) TMF_HIP(hipMemcpyAsync(base + off[3 * i + 1], fr[i].in1, ib, hipMemcpyHostToDevice, st));
     }
-    plan_ragged(dv, block, kind, table, chunks, keys);
-    HostCall hc((int64_t)chunks.size(), st, n_lapack);
-    if (int rc = run_ragged(block, alpha, kind, st, route, hc.report(), table, chunks, keys, px)) return rc;
+    plan_parts(dv);
+    std::vector<std::unique_ptr<HostCall>> hc;
+    for (Part &p : parts) {
+        hc.emplace_back(new HostCall((int64_t)p.plan.chunks.size(), st, &p.n));
+        t_list_pass = 0;
+        if (int rc = run_ragged(block, alpha, st, hc.back()->report(), p.plan, px)) return rc;
+        if (!hc.back()->sink.p) total_list += t_list_pass;  // read back by the passes themselves
+    }
     for (size_t i = 0; i < fr.size(); ++i) {
         if (!fr[i].has_work(kind, block)) continue;
         TMF_HIP(hipMemcpyAsync(fr[i].out, dv[i].out, (size_t)fr[i].out_bytes(kind, block), hipMemcpyDeviceToHost, st));
         if (const size_t kb = (size_t)fr[i].out2_bytes(kind, block))
             TMF_HIP(hipMemcpyAsync(fr[i].out2, dv[i].out2, kb, hipMemcpyDeviceToHost, st));
     }
-    return hc.finish();
+    for (size_t k = 0; k < parts.size(); ++k) {
+        if (int rc = hc[k]->finish()) return rc;
+        if (hc[k]->sink.p && hc[k]->nchunks) total_list += t_list_pass;
+        total_n += parts[k].n;
+    }
+    if (n_lapack) *n_lapack = total_n;
+    t_list_pass = total_list;
+    return 0;
 }
 
 // ---- ragged tile preparation (tmfwm_tile_plan.h)
@@ -2010,6 +2110,26 @@ int tmfwm_embed_key_ragged(const tmfwm_embed_key_frame *frames, int64_t n_frames
                            void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
 {
     if (int rc = check_ragged_call(frames, n_frames, block, alpha, RKind::EmbedKey, mem_kind, route, n_lapack_blocks)) return rc;
+    std::vector<RFrame> fr((size_t)n_frames);
+    for (int64_t i = 0; i < n_frames; ++i)
+        fr[(size_t)i] = {frames[i].rgb, frames[i].wm_tile, frames[i].out, frames[i].height, frames[i].width,
+                         reinterpret_cast<uint8_t *>(frames[i].out_key)};
+    return ragged_call(fr, block, alpha, RKind::EmbedKey, mem_kind, hip_stream, route, n_lapack_blocks);
+}
+
+int tmfwm_embed_ragged_rank1(const tmfwm_embed_frame *frames, int64_t n_frames, int32_t block, double alpha, int32_t mem_kind,
+                             void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    if (int rc = check_ragged_call(frames, n_frames, block, alpha, RKind::Embed, mem_kind, route, n_lapack_blocks, true)) return rc;
+    std::vector<RFrame> fr((size_t)n_frames);
+    for (int64_t i = 0; i < n_frames; ++i) fr[(size_t)i] = {frames[i].rgb, frames[i].wm_tile, frames[i].out, frames[i].height, frames[i].width};
+    return ragged_call(fr, block, alpha, RKind::Embed, mem_kind, hip_stream, route, n_lapack_blocks);
+}
+
+int tmfwm_embed_key_ragged_rank1(const tmfwm_embed_key_frame *frames, int64_t n_frames, int32_t block, double alpha, int32_t mem_kind,
+                                 void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    if (int rc = check_ragged_call(frames, n_frames, block, alpha, RKind::EmbedKey, mem_kind, route, n_lapack_blocks, true)) return rc;
     std::vector<RFrame> fr((size_t)n_frames);
     for (int64_t i = 0; i < n_frames; ++i)
         fr[(size_t)i] = {frames[i].rgb, frames[i].wm_tile, frames[i].out, frames[i].height, frames[i].width,

@@ -48,6 +48,72 @@ struct RaggedKeyArgs : RaggedArgs {
     float *const *keys;
 };
 
+// ---- the list pass of the ragged rank-1 route (TMFWM_ROUTE_RANK1, tmfwm_ragged_pre.hip)
+//
+// The blocks the ragged pre-pass leaves go to a slow list of the chunk, segmented over the
+// kListShards append counters of the single-size list passes (tmfwm_internal.h), but dealt per
+// frame: frame i of the chunk owns the shards [sh0, sh0 + n) and its block row bi appends to shard
+// sh0 + bi % n, so a list wave (one per shard) holds blocks of one frame and works on that frame's
+// one-frame view, wave-uniform as in the strip pass.  A shard's segment of the list starts at
+// ragged_seg_base: the frame's own id range [block0, block0 + nbh * nbw) cut at whole rows, so a
+// segment's capacity is exactly what its rows can append.
+struct RaggedShards {
+    uint32_t sh0, n;  // n = 0: a frame without a block (it shares its successor's sh0 and is never found)
+};
+
+// a chunk holds at most this many frames with blocks: each needs a shard of its own
+inline bool ragged_shards_full(int64_t frames_with_blocks) { return frames_with_blocks >= (int64_t)kListShards; }
+
+// first slot of shard k (0 <= k <= n) of a frame whose nbh rows of nbw blocks are dealt round-robin
+// over its n shards (shard k: rows k, k + n, ...)
+__host__ __device__ inline uint32_t ragged_seg_base(uint32_t block0, uint32_t nbh, uint32_t nbw, uint32_t n, uint32_t k)
+{
+    const uint32_t q = nbh / n, r = nbh % n;
+    return block0 + (k * q + (k < r ? k : r)) * nbw;
+}
+
+// The shard ranges of a chunk's frames f[0 .. n): one shard per frame with blocks, and the
+// kListShards - (frames with blocks) left over in proportion to the frames' block rows, at most
+// one shard per row.  Returns the shards used (<= kListShards; the caller has kept the chunk to
+// kListShards frames with blocks, ragged_shards_full).
+template <class Frame>
+inline uint32_t ragged_plan_shards(const Frame *f, int64_t n, RaggedShards *out)
+{
+    uint64_t rows = 0, with_blocks = 0;
+    for (int64_t i = 0; i < n; ++i)
+        if (f[i].nbh > 0 && f[i].nbw > 0) rows += (uint64_t)f[i].nbh, ++with_blocks;
+    const uint64_t spare = (uint64_t)kListShards - with_blocks;
+    uint32_t used = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        uint32_t s = 0;
+        if (f[i].nbh > 0 && f[i].nbw > 0) {
+            const uint64_t extra = spare * (uint64_t)f[i].nbh / rows, most = (uint64_t)f[i].nbh - 1;
+            s = 1 + (uint32_t)(extra < most ? extra : most);
+        }
+        out[i] = RaggedShards{used, s};
+        used += s;
+    }
+    return used;
+}
+
+// the pre-pass and list-pass kernels' arguments: RaggedArgs, the shard side table (indexed as
+// `frames`, as RaggedKeyArgs::keys is) and the chunk's slow list (all null on
+// TMFWM_ROUTE_RANK1_REFERENCE: a left block goes straight to fb_list)
+struct RaggedRank1Args : RaggedArgs {
+    const RaggedShards *shards;
+    uint32_t *slow_list;
+    uint32_t *slow_count;
+    uint32_t *slow_shards;
+};
+
+// the ragged pre-pass over a chunk's `waves` strip waves, then -- r.slow_list set -- the list pass
+// over the `shards` shards the chunk uses
+hipError_t launch_embed_rank1_ragged(const RaggedRank1Args &r, int64_t waves, uint32_t shards, hipStream_t st);
+template <int B>
+hipError_t embed_rank1_ragged_b(const RaggedRank1Args &r, unsigned waves, hipStream_t st);
+template <int B>
+hipError_t embed_ragged_list_b(const RaggedRank1Args &r, unsigned shards, hipStream_t st);
+
 // blocks per strip wave at this block size (Geo<b>::BPW): the host needs it for strips_per_row
 int ragged_strip_blocks(int block);
 // strip pass of a chunk: `waves` = the chunk's strip waves (> 0), one workgroup each
@@ -106,6 +172,9 @@ __device__ __forceinline__ RaggedFrameK *ragged_const(const RaggedFrame *p) { re
 // the key side table the same way (RaggedKeyArgs::keys)
 using RaggedKeyK = float *const TMF_CONST_AS;
 __device__ __forceinline__ RaggedKeyK *ragged_key_const(float *const *p) { return (RaggedKeyK *)p; }
+// and the shard side table (RaggedRank1Args::shards)
+using RaggedShardsK = const TMF_CONST_AS RaggedShards;
+__device__ __forceinline__ RaggedShardsK *ragged_shards_const(const RaggedShards *p) { return (RaggedShardsK *)p; }
 
 // the frame that owns flat index x: the last i in [0, n) with prefix(i) <= x (frames with
 // nothing to do share their successor's prefix and are never found)

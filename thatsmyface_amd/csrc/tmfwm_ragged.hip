@@ -19,6 +19,15 @@ hipError_t launch_embed_ragged(const RaggedArgs &r, int64_t waves, hipStream_t s
     return for_block(r.block, [&](auto b) { return embed_ragged_b<b()>(r, (unsigned)waves, st); });
 }
 
+hipError_t launch_embed_rank1_ragged(const RaggedRank1Args &r, int64_t waves, uint32_t shards, hipStream_t st)
+{
+    if (waves <= 0 || waves > kGridMax || shards > kListShards || (r.slow_list && shards == 0)) return hipErrorInvalidValue;
+    return for_block(r.block, [&](auto b) {
+        const hipError_t e = embed_rank1_ragged_b<b()>(r, (unsigned)waves, st);
+        return e != hipSuccess || !r.slow_list ? e : embed_ragged_list_b<b()>(r, shards, st);
+    });
+}
+
 hipError_t launch_embed_key_ragged(const RaggedKeyArgs &r, int64_t waves, hipStream_t st)
 {
     if (waves <= 0 || waves > kGridMax) return hipErrorInvalidValue;

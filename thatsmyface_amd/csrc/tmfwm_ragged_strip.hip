@@ -12,7 +12,7 @@
 // keyed_sigma<B, kPowerIters> on that frame's one-frame view.
 #include "tmfwm_keyed.h"
 #include "tmfwm_passes.h"
-#include "tmfwm_ragged.h"
+#include "tmfwm_ragged_strips.h"
 
 #ifndef TMF_B
 #error "TMF_B: the block size of this translation unit"
@@ -22,26 +22,6 @@
 #endif
 
 namespace tmf {
-
-// this wave's strip of frame f (frame index 0 of the one-frame view) and its first block's id
-template <int B>
-TMF_DEVI StripPos ragged_strip_pos(RaggedFrameK *f, uint32_t &id)
-{
-    const uint32_t w = blockIdx.x - f->wave0, spr = (uint32_t)f->strips_per_row;
-    StripPos p;
-    p.frame = 0;
-    p.bi = (int)(w / spr);
-    p.bj = (int)(w % spr) * Geo<B>::BPW + (int)(threadIdx.x & 63) / Geo<B>::L;
-    p.valid = p.bj < f->nbw;
-    id = f->block0 + (uint32_t)p.bi * (uint32_t)f->nbw + (uint32_t)p.bj;
-    return p;
-}
-
-TMF_DEVI RaggedFrameK *ragged_wave_frame(const RaggedArgs &r)
-{
-    RaggedFrameK *tab = ragged_const(r.frames);
-    return tab + ragged_find(r.nframes, blockIdx.x, [&](int i) { return tab[i].wave0; });
-}
 
 #if TMF_RAGGED_PART & 1
 template <int B>

@@ -1,4 +1,5 @@
-// The rank-1 pre-pass of the hybrid route (TMFWM_ROUTE_RANK1, round 6): photo mode.
+// The rank-1 pre-pass of the hybrid route (TMFWM_ROUTE_RANK1, round 6), photo mode,
+// as a device function.
 //
 // The reference reconstructs every block from all of LAPACK's factors rounded to f32
 // (watermarking.py:195-201), but only S[0] changes, so its M_ref = fl(U32 fl(S'32 Vt32)) is
@@ -29,21 +30,27 @@
 // SVD, byte certificate, dgesdd route (TMFWM_ROUTE_RANK1) -- or straight to the dgesdd route
 // (TMFWM_ROUTE_RANK1_REFERENCE, no Jacobi factors and so no K), so every byte is the reference's
 // either way.
-// (tmfwm_rank1.h holds this kernel's body a second time, for the ragged pre-pass: keep the two in step.)
+//
+// This is the body of embed_rank1_kernel<B> (tmfwm_rank1.hip) written out a second time, as a
+// device function for the ragged pre-pass kernel (tmfwm_ragged_pre.hip), which decides only where
+// a block the pass leaves is appended.  With the single-size kernel calling this function too,
+// that kernel's register allocation moved at b = 6, 8, 10, 12, 14 and 16 (b = 14: 200 -> 222
+// VGPRs, b = 8: 53 -> 60 SGPRs), by reference or by value, so it keeps its own copy, as
+// embed_key_kernel does (tmfwm_blocks.h).  A change to the pass goes into both, statement for
+// statement: tests/test_ragged_rank1_gpu.py holds the two to the same bytes and the same counts.
+#pragma once
 #include "tmfwm_blocks.h"
 #include "tmfwm_idct_bounds.h"
 
 namespace tmf {
 
-extern template __global__ void embed_kernel<8, true>(EmbedArgs);  // tmfwm_embed8.hip
-// the list passes of the other sizes exist for this route only (the hybrid route's strip pass
-// there runs every block to the end, kDeferMax<b> = 0): instantiated in tmfwm_rank1_lists.hip
-extern template __global__ void embed_kernel<4, true>(EmbedArgs);
-extern template __global__ void embed_kernel<6, true>(EmbedArgs);
-extern template __global__ void embed_kernel<10, true>(EmbedArgs);
-extern template __global__ void embed_kernel<12, true>(EmbedArgs);
-extern template __global__ void embed_kernel<14, true>(EmbedArgs);
-extern template __global__ void embed_kernel<16, true>(EmbedArgs);
+template <int B>
+constexpr int kRank1Waves = B <= 8 ? 3 : 2;  // waves per SIMD of the pre-pass kernels
+// LDS of a pre-pass wave: the transpose tiles, and the source bytes until the colour phase
+template <int B>
+constexpr int kRank1LdsFloats = Geo<B>::BPW * B * (B + 1);
+template <int B>
+constexpr int kRank1PixWords = Geo<B>::R * Geo<B>::NW;
 
 constexpr int kRank1Iters = 4;  // f64 power steps before the a-posteriori test
 // LAPACK's two measured constants (tools/exp/lapack_bounds.py, profiles/r06/lapack_bounds_b*.json;
@@ -59,18 +66,17 @@ TMF_DEVI float row_value(const float (&own)[kRows<B, L>])
     return group_bcast<L, K / R>(own[K % R]);
 }
 
-template <int B>
-__global__ __launch_bounds__(64, B <= 8 ? 3 : 2) void embed_rank1_kernel(EmbedArgs a)
+// The pre-pass on this wave's blocks (pos per lane; lds: kRank1LdsFloats<B> floats, pix:
+// kRank1PixWords<B> rows of 64 words): a kept block's pixels are stored; a block the pass leaves
+// wrote nothing, and its first lane calls left(), which appends it to the caller's list.
+template <int B, class Left>
+TMF_DEVI void embed_rank1_blocks(const EmbedArgs &a, const StripPos &pos, float *lds, uint32_t (*pix)[64], Left left)
 {
-    constexpr int L = Geo<B>::L, R = Geo<B>::R, BPW = Geo<B>::BPW, LD = B + 1, NW = Geo<B>::NW;
+    constexpr int L = Geo<B>::L, R = Geo<B>::R, LD = B + 1, NW = Geo<B>::NW;
     constexpr double u53 = 1.1102230246251565e-16;  // 2^-53
     constexpr float u24 = 5.9604644775390625e-08f;  // 2^-24
-    __shared__ float lds[BPW * B * LD];
-    __shared__ uint32_t pix[R * NW][64];
     const int lane = threadIdx.x & 63, g = lane / L, q = lane % L;
     float *tile = lds + g * B * LD;
-    const StripPos pos = strip_pos<B>(a.strips_per_row, a.nbw);
-    const uint32_t id = (uint32_t)(((int64_t)blockIdx.y * a.nbh + pos.bi) * a.nbw + pos.bj);
     const uint8_t *src = a.src + pos.frame * a.frame_stride;
     uint8_t *dst = a.dst + pos.frame * a.frame_stride;
 
@@ -289,33 +295,8 @@ __global__ __launch_bounds__(64, B <= 8 ? 3 : 2) void embed_rank1_kernel(EmbedAr
             if (real_row<B>(q, r)) store_words<B>(pp, a.aligned, outw[r]);
         }
     } else if (q == 0) {
-        if (a.slow_list) {  // TMFWM_ROUTE_RANK1: the full hybrid route in the list pass
-            const uint32_t row = blockIdx.y * (uint32_t)a.nbh + (uint32_t)pos.bi, s = row % kListShards;
-            a.slow_list[shard_base(s, (uint32_t)a.nframes * (uint32_t)a.nbh, (uint32_t)a.nbw) +
-                        atomicAdd(a.slow_shards + s * kShardStride, 1u)] = id;
-        } else {  // TMFWM_ROUTE_RANK1_REFERENCE: the dgesdd route (embed_fixup_kernel)
-            a.fb_list[atomicAdd(a.fb_count, 1u)] = id;
-        }
+        left();
     }
-}
-
-bool rank1_block(int block) { return block >= 4 && block <= 16 && block % 2 == 0; }
-
-// The rank-1 pre-pass over every block (every slider size, b = 4..16 even), then the edge pixels.  TMFWM_ROUTE_RANK1
-// (a.slow_list set): the list pass (embed_kernel<b, true>: the full hybrid route) over the blocks
-// it left; TMFWM_ROUTE_RANK1_REFERENCE (no slow list): those blocks went to the dgesdd-route list.
-// Either way the caller runs the dgesdd-route fixup next.  The caller handles other block sizes.
-hipError_t launch_embed_rank1(EmbedArgs a, hipStream_t st)
-{
-    if (!rank1_block(a.block)) return hipErrorInvalidValue;
-    if (a.nbh > 0 && a.nbw > 0) {
-        // TMFWM_ROUTE_RANK1: the list pass over the blocks the pre-pass left
-        const hipError_t e = for_block(a.block, [&](auto b) {
-            return launch_strips(a, Geo<b()>::BPW, embed_rank1_kernel<b()>, embed_kernel<b(), true>, st);
-        });
-        if (e != hipSuccess) return e;
-    }
-    return launch_edges(a.src, a.dst, a.nframes, a.H, a.W, a.frame_stride, a.block, st);
 }
 
 }  // namespace tmf

@@ -179,11 +179,14 @@ class RaggedGpuStage(GpuStage):
             tiles = self._group_tiles(keys)
             dev_in = [h.to(self.device, non_blocking=True) for h in host_in]
             dev_key = []
+            # the rank-1 routes have ragged calls of their own (batch.embed_ragged_rank1)
+            rank1 = self.route in ("rank1", "rank1_reference")
             if self.return_keys:
-                dev_out, dev_key = self.batch.embed_with_key_ragged(dev_in, tiles, self.block, self.alpha, stream=self.stream,
-                                                                    route=self.route)
+                embed = self.batch.embed_with_key_ragged_rank1 if rank1 else self.batch.embed_with_key_ragged
+                dev_out, dev_key = embed(dev_in, tiles, self.block, self.alpha, stream=self.stream, route=self.route)
             else:
-                dev_out = self.batch.embed_ragged(dev_in, tiles, self.block, self.alpha, stream=self.stream, route=self.route)
+                embed = self.batch.embed_ragged_rank1 if rank1 else self.batch.embed_ragged
+                dev_out = embed(dev_in, tiles, self.block, self.alpha, stream=self.stream, route=self.route)
             for ho, do in zip(host_out + host_key, list(dev_out) + list(dev_key)):
                 ho.copy_(do, non_blocking=True)
             done = torch.cuda.Event()
@@ -261,7 +264,9 @@ class KeyedExtractStage:
                 k0 = key_at[id(keys[j])]
                 dkeys.append(dev_in[k0:k0 + 4 * nbh * nbw].view(torch.float32).view(nbh, nbw))
                 outs.append(dev_out[o:o + nbh * nbw].view(nbh, nbw))
-            self.batch.extract_keyed_ragged(frames, dkeys, b, self.alpha, out=outs, stream=self.stream, route=self.route)
+            # on a rank-1 route the keyed extract is the hybrid enclosure, as every single-size keyed call has it
+            route = "hybrid" if self.route in ("rank1", "rank1_reference") else self.route
+            self.batch.extract_keyed_ragged(frames, dkeys, b, self.alpha, out=outs, stream=self.stream, route=route)
             host_out.copy_(dev_out, non_blocking=True)
             done = torch.cuda.Event()
             done.record(self.stream)

@@ -8,6 +8,11 @@ QR-like watermark as PNG bytes, preserve_ratio=True, b=8, alpha=0.1.
               (embed_watermark_page.py:492-558 without its 0.1 s UI sleep)
   pipelined : pipeline.embed_images (decode / encode thread pools, side-stream GPU)
 Prints one JSON line (images/s for both, equality of the PNG bytes).
+
+--batch-images K --routes R1 R2 ...: instead, pipeline.embed_images(batch_images=K) with
+custom_settings["svd_route"] = each route in turn, the routes alternating over --rounds rounds in
+this one process; one JSON line with every route's median images/s, its A/A spread (the medians
+of its even and odd rounds as a ratio) and whether all routes gave the same PNG bytes.
 """
 import argparse
 import io
@@ -30,6 +35,9 @@ def main():
     p.add_argument("--height", type=int, default=1080)
     p.add_argument("--width", type=int, default=1920)
     p.add_argument("--workers", type=int, default=16)
+    p.add_argument("--batch-images", type=int, default=None)
+    p.add_argument("--routes", nargs="+", default=None)
+    p.add_argument("--rounds", type=int, default=6)
     a = p.parse_args()
     from lapack_path import photo_cover
 
@@ -45,6 +53,24 @@ def main():
     Image.fromarray((np.random.default_rng(1).integers(0, 2, (29, 29)) * 255).astype(np.uint8), "L").save(wbuf, format="PNG")
     wm = wbuf.getvalue()
     settings = {"block_size": 8, "alpha": 0.1}
+    if a.routes:
+        import statistics
+
+        times, first = {r: [] for r in a.routes}, {}
+        for r in a.routes:  # warm-up, and the bytes to compare
+            first[r] = pipeline.embed_images(pngs, wm, True, {**settings, "svd_route": r}, workers=a.workers, batch_images=a.batch_images)
+        for _ in range(a.rounds):
+            for r in a.routes:
+                t0 = time.perf_counter()
+                pipeline.embed_images(pngs, wm, True, {**settings, "svd_route": r}, workers=a.workers, batch_images=a.batch_images)
+                times[r].append(time.perf_counter() - t0)
+        same = all(x.png == y.png for r in a.routes[1:] for x, y in zip(first[a.routes[0]], first[r]))
+        print(json.dumps({"images": a.images, "size": f"{a.width}x{a.height}", "workers": a.workers, "batch_images": a.batch_images,
+                          "rounds": a.rounds,
+                          "img_per_s": {r: round(a.images / statistics.median(t), 2) for r, t in times.items()},
+                          "aa": {r: round(statistics.median(t[0::2]) / statistics.median(t[1::2]), 4) for r, t in times.items()},
+                          "png_bytes_identical": same}))
+        return
     pipeline.embed_images(pngs[:2], wm, True, settings, workers=a.workers)  # warm-up (library, tile, allocator)
     t0 = time.perf_counter()
     seq = []

@@ -20,12 +20,17 @@ Workload E (enrolment): workload A's frames and tiles.  embed_with_
 embed_ragged followed by sigma1_map_ragged (the two-pass way to the same outputs and keys; its
 time is reported as "base"), and against embed_ragged alone (what the key costs).
 
+Workload R (the rank-1 routes): workload A's frames and tiles at b = 8 and b = 16.
+embed_ragged_rank1 on "rank1" against embed_ragged on "hybrid" (base), on "rank1_reference" against
+embed_ragged on "reference" (base), and each of the two against the loop of 64 single-frame
+embed_batch calls on the same rank-1 route (base).
+
 Both arms of a comparison run alternately in one process, each timing a window of `inner` calls
 that ends in a device synchronise.  Every ratio comes with the A/A spread of its own run: the
 medians of the even and of the odd rounds of the same arm, as a ratio.  The arms' outputs are
 compared byte for byte before anything is timed.
 
-usage: python tools/ragged_bench.py [--workload a|b|k|e|ab|abk] [--rounds R] [--frames-b N]
+usage: python tools/ragged_bench.py [--workload a|b|k|e|r|ab|abk] [--rounds R] [--frames-b N]
 """
 import argparse
 import json
@@ -175,6 +180,56 @@ def workload_e(rounds, dev):
                     {"what": "64 images enrolment: embed_with_key_ragged vs embed_ragged alone (base)", **extra})]
 
 
+def workload_r(rounds, dev):
+    alpha, n = 0.1, 64
+    out = []
+    for b in (8, 16):
+        picks, frames, tiles = frames_a(dev, b, n)
+        frames1 = [f[None] for f in frames]
+        state = {}
+
+        def loop(route):
+            return lambda: state.__setitem__("loop_" + route, [batch.embed_batch(f, t, b, alpha, route=route) for f, t in zip(frames1, tiles)])
+
+        arms = {
+            "hybrid": lambda: state.__setitem__("hybrid", batch.embed_ragged(frames, tiles, b, alpha, route="hybrid")),
+            "reference": lambda: state.__setitem__("reference", batch.embed_ragged(frames, tiles, b, alpha, route="reference")),
+            "rank1": lambda: state.__setitem__("rank1", batch.embed_ragged_rank1(frames, tiles, b, alpha, route="rank1")),
+            "rank1_reference": lambda: state.__setitem__("rank1_reference",
+                                                         batch.embed_ragged_rank1(frames, tiles, b, alpha, route="rank1_reference")),
+            "loop_rank1": loop("rank1"),
+            "loop_rank1_reference": loop("rank1_reference"),
+        }
+        for fn in arms.values():
+            fn()
+        torch.cuda.synchronize()
+        for i in range(n):  # every route gives the reference's bytes
+            for k in ("hybrid", "rank1", "rank1_reference"):
+                assert torch.equal(state[k][i], state["reference"][i]), (k, "differs from the reference route", b, i)
+            for k in ("loop_rank1", "loop_rank1_reference"):
+                assert torch.equal(state[k][i][0], state["reference"][i]), (k, "differs from the reference route", b, i)
+        st = {}
+        for route in ("rank1", "rank1_reference"):
+            s1 = {}
+            batch.embed_ragged_rank1(frames, tiles, b, alpha, stats=s1, route=route)
+            st[route] = s1
+        blocks = sum((h // b) * (w // b) for h, w in picks)
+        extra = {"block": b, "megapixels": round(sum(h * w for h, w in picks) / 1e6, 1), "blocks": blocks, "outputs_equal": True,
+                 "stats": st}
+        out += [compare("R1", {"base": arms["hybrid"], "ragged": arms["rank1"]}, 10, rounds,
+                        {"what": "64 images embed: embed_ragged_rank1 rank1 vs embed_ragged hybrid (base)", **extra}),
+                compare("R2", {"base": arms["reference"], "ragged": arms["rank1_reference"]}, 2, rounds,
+                        {"what": "64 images embed: embed_ragged_rank1 rank1_reference vs embed_ragged reference (base)", **extra}),
+                compare("R3", {"base": arms["loop_rank1"], "ragged": arms["rank1"]}, 10, rounds,
+                        {"what": "64 images embed: embed_ragged_rank1 rank1 vs loop of single-frame embed_batch rank1 (base)", **extra}),
+                compare("R4", {"base": arms["loop_rank1_reference"], "ragged": arms["rank1_reference"]}, 10, rounds,
+                        {"what": "64 images embed: embed_ragged_rank1 rank1_reference vs loop of single-frame embed_batch "
+                                 "rank1_reference (base)", **extra})]
+        del frames, tiles, frames1, state
+        torch.cuda.empty_cache()
+    return out
+
+
 def workload_b(rounds, dev, n):
     out = []
     for cover in ("noise", "photo"):
@@ -208,7 +263,7 @@ def workload_b(rounds, dev, n):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", default="ab", choices=("a", "b", "k", "e", "ab", "abk"))
+    ap.add_argument("--workload", default="ab", choices=("a", "b", "k", "e", "r", "ab", "abk"))
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--frames-b", type=int, default=256)
     a = ap.parse_args()
@@ -224,6 +279,8 @@ def main():
         workload_k(a.rounds, dev)
     if "e" in a.workload:
         workload_e(a.rounds, dev)
+    if "r" in a.workload:
+        workload_r(a.rounds, dev)
 
 
 if __name__ == "__main__":

@@ -18,7 +18,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 SIZES = (4, 6, 8, 10, 12, 14, 16)
 # compiled once per block size with -DTMF_B=<b> (the Makefile's PER_SIZE)
-PER_SIZE = ("tmfwm_fixup.hip", "tmfwm_ragged_fixup.hip", "tmfwm_keyed_fixup.hip", "tmfwm_ragged_strip.hip", "tmfwm_embed_key.hip")
+PER_SIZE = ("tmfwm_fixup.hip", "tmfwm_ragged_fixup.hip", "tmfwm_keyed_fixup.hip", "tmfwm_ragged_strip.hip", "tmfwm_embed_key.hip",
+            "tmfwm_ragged_pre.hip")
 KEYS = ["TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill",
         "LDS Size [bytes/block]"]
 
@@ -31,6 +32,8 @@ def units(csrc):
             for b in SIZES:
                 if (tu, b) == ("tmfwm_ragged_strip.hip", 8):  # two objects: embed / extract under max-ILP, the keyed kernels not
                     out += [(tu, ["-DTMF_B=8", "-DTMF_RAGGED_PART=1"] + ILP), (tu, ["-DTMF_B=8", "-DTMF_RAGGED_PART=2"])]
+                elif (tu, b) == ("tmfwm_ragged_pre.hip", 8):  # two objects: the pre-pass, and the list pass under max-ILP
+                    out += [(tu, ["-DTMF_B=8", "-DTMF_RAGGED_PRE_PART=1"]), (tu, ["-DTMF_B=8", "-DTMF_RAGGED_PRE_PART=2"] + ILP)]
                 elif (tu, b) == ("tmfwm_embed_key.hip", 8):  # under max-ILP, as embed_kernel<8>
                     out.append((tu, ["-DTMF_B=8"] + ILP))
                 else:
