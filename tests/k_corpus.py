@@ -82,7 +82,7 @@ def ratios(D: np.ndarray):
     return cert, ru, rv, rs
 
 
-# The rank-1 pre-pass's LAPACK constants (csrc/tmfwm_rank1.hip: gamma' = 2^-40 s1, the top pair
+# The rank-1 pre-pass's LAPACK constants (csrc/tmfwm_rank1.h: gamma' = 2^-40 s1, the top pair
 # within 1024 2^-53 s1 / (s1 - s2)), measured by tools/exp/lapack_bounds.py
 RESID_UNITS = 8192
 PAIR_UNITS = 1024

@@ -1,6 +1,6 @@
 """Blocks whose rank-1 pre-pass decision is known in advance -- test infrastructure only.
 
-The pre-pass (thatsmyface_amd/csrc/tmfwm_rank1.hip) keeps a block's bytes when its
+The pre-pass (thatsmyface_amd/csrc/tmfwm_rank1_body.h) keeps a block's bytes when its
 gate passes (a zero block, or gap > 0, g1 > 0 and eps_uv <= 2^-30) and every pixel has the same
 three bytes at both ends of [Y_fast - eps_Y, Y_fast + eps_Y]; it hands every other block on, and
 the routes count those (`lapack_blocks` on rank1_reference, `list_pass_blocks` on rank1).  Blocks

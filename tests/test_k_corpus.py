@@ -71,7 +71,7 @@ def test_newton_scaled_test_fixes_graded_outlier():
 @pytest.mark.parametrize("b", [4, 6, 8, 10, 12, 14, 16])
 @pytest.mark.parametrize("kind", kc.PIXEL_KINDS + kc.DCT_KINDS)
 def test_lapack_constants_of_the_rank1_prepass(b, kind):
-    """The rank-1 pre-pass (csrc/tmfwm_rank1.hip) assumes LAPACK's residual
+    """The rank-1 pre-pass (csrc/tmfwm_rank1.h) assumes LAPACK's residual
     |U S V^T - D| <= 8192 units of 2^-53 sigma_1 and its top pair within 1024 units of
     2^-53 sigma_1 / (sigma_1 - sigma_2) (the latter through the Jacobi route's pair: the direct
     difference).  Both at most half their constant on the seeded classes (the study at scale:

@@ -34,3 +34,20 @@ def test_valu_embed8_strip_and_list_pass(tmp_path):
 def test_valu_embed16(tmp_path):
     e = _valu(tmp_path, 16)["embed_kernel<16>"]
     assert e["valu_instr_per_wave"] == 39033.4 and "list_pass" not in e
+
+
+def test_asm_diff_strips_and_counts():
+    """tools/asm_diff.py compares code lines only: comments, directives, local labels and the
+    per-unit __hip_cuid_* symbol do not count, a changed instruction counts on both sides."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import asm_diff
+    finally:
+        sys.path.pop(0)
+    a = "\t.text\n; a comment\n_Z1kv:\n\ts_load_dword s0, s[4:5], 0x0\n.LBB0_1:\n\tv_add_f32 v0, v1, v2 ; kept\n\n__hip_cuid_1a2b:\n\ts_endpgm\n"
+    same = "\t.amdgcn_target \"x\"\n_Z1kv:\n; another\n\ts_load_dword s0, s[4:5], 0x0\n.LBB0_7:\n\tv_add_f32 v0, v1, v2 ; kept\n__hip_cuid_ffff:\n\ts_endpgm\n\t.p2align 8\n"
+    other = same.replace("v_add_f32 v0, v1, v2", "v_add_f32 v0, v2, v1") + "\ts_nop 0\n"
+    assert asm_diff.strip_asm(a) == ["_Z1kv:", "s_load_dword s0, s[4:5], 0x0", "v_add_f32 v0, v1, v2 ; kept", "s_endpgm"]
+    assert asm_diff.differing_lines(a, same) == 0
+    assert asm_diff.differing_lines(a, other) == 3  # the instruction on both sides, and the added line
+    assert asm_diff.differing_lines(a, "") == 4

@@ -97,11 +97,16 @@ def test_lapack_constants_agree_and_keep_their_margins():
     import k_corpus as kc
     import lapack_bounds as LB
 
-    with open(os.path.join(ROOT, "thatsmyface_amd", "csrc", "tmfwm_rank1.hip")) as f:
-        src = f.read()
-    named = {m.group(1): float(m.group(2)) for m in re.finditer(r"constexpr double (kRank1\w+Units) = ([0-9.]+);", src)}
-    assert named == {"kRank1ResidUnits": float(kc.RESID_UNITS), "kRank1PairUnits": float(kc.PAIR_UNITS)}, named
-    # the names are what the kernel uses: the bare literals are gone from its code (comments aside)
+    # the pre-pass's whole source: the constants' home, the one body, and its two kernels
+    src = ""
+    for name in ("tmfwm_rank1.h", "tmfwm_rank1_body.h", "tmfwm_rank1.hip", "tmfwm_ragged_pre.hip"):
+        with open(os.path.join(ROOT, "thatsmyface_amd", "csrc", name)) as f:
+            src += f.read() + "\n"
+    defs = re.findall(r"constexpr double (kRank1\w+Units) = ([0-9.]+);", src)
+    named = sorted((n, float(v)) for n, v in defs)  # a list: a second definition anywhere fails
+    assert named == [("kRank1PairUnits", float(kc.PAIR_UNITS)), ("kRank1ResidUnits", float(kc.RESID_UNITS))], named
+    # the names are what the kernels use: over the four files each occurs twice, one definition
+    # and one use (the body is one text), and the bare literals are gone (comments aside)
     code = "\n".join(line.split("//")[0] for line in src.splitlines())
     assert code.count("kRank1ResidUnits") == 2 and code.count("kRank1PairUnits") == 2
     assert "0x1p-40f * s1f" not in code and "1024.0 * u53" not in code

@@ -53,7 +53,7 @@ def test_fast_path_certificate_is_sound():
 
 @pytest.mark.parametrize("b", [4, 6, 8, 10, 12, 14, 16])
 def test_rank1_prepass_bound_is_sound(b):
-    """The shipped rank-1 pre-pass's bound (csrc/tmfwm_rank1.hip) restated in numpy
+    """The shipped rank-1 pre-pass's bound (csrc/tmfwm_rank1.h, tmfwm_rank1_body.h) restated in numpy
     (fastpath_study.certify_rank1, the IDCT's rounding through tools/exp/idct_bound.py's tables):
     every block it decides has the dgesdd route's bytes, at every slider size, with the noise and
     a binary (0 / 255) watermark; it decides most camera-like blocks under the noise watermark

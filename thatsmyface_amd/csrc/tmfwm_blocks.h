@@ -831,73 +831,21 @@ TMF_DEVI void embed_blocks(const EmbedArgs &a, const StripPos &pos, uint32_t id,
     stamp(6);
 }
 
+// The embed pass: the strip pass (one wave per strip) or, LIST, the list pass over the slow list's
+// shards.  Its body is a fragment that the key variant includes too (tmfwm_embed_pass_body.h).
 template <int B, bool LIST = false>
 __global__ __launch_bounds__(64, kEmbedWaves<B>) void embed_kernel(EmbedArgs a)
 {
-    constexpr int L = Geo<B>::L, BPW = Geo<B>::BPW, TS = kEmbedTS<B>;
-    // the transpose tiles (also svd3's scratch during the SVD), then the source bytes / the
-    // upper-end tiles, in one array (the reconstruction picks a tile by an offset)
-    __shared__ __attribute__((aligned(16))) float lds_all[BPW * TS + kHiPad<B> + kLds2Floats<B>];
-    float *lds = lds_all, *lds2 = lds_all + BPW * TS + kHiPad<B>;
-    if constexpr (LIST) {
-        // grid-stride over the slow list's segments (their lengths are known on the device only)
-        const uint32_t per_frame = (uint32_t)a.nbh * (uint32_t)a.nbw, rows = (uint32_t)a.nframes * (uint32_t)a.nbh;
-        const int g = (threadIdx.x & 63) / L;
-        for (uint32_t s = blockIdx.x; s < kListShards; s += gridDim.x) {
-            const uint32_t n = a.slow_shards[s * kShardStride], base = shard_base(s, rows, (uint32_t)a.nbw);
-            if (n != 0 && (threadIdx.x & 63) == 0) atomicAdd(a.slow_count, n);
-            for (uint32_t t0 = 0; t0 < n; t0 += BPW) {
-                StripPos pos;
-                pos.valid = t0 + g < n;
-                const uint32_t id = pos.valid ? a.slow_list[base + t0 + g] : 0u;
-                pos.frame = id / per_frame;
-                const uint32_t rem = id % per_frame;
-                pos.bi = (int)(rem / (uint32_t)a.nbw);
-                pos.bj = (int)(rem % (uint32_t)a.nbw);
-                embed_blocks<B, true>(a, pos, id, lds, lds2);
-                __syncthreads();  // the LDS tiles are reused by the next listed blocks
-            }
-        }
-    } else {
-        const StripPos pos = strip_pos<B>(a.strips_per_row, a.nbw);
-        const uint32_t id = (uint32_t)(((int64_t)blockIdx.y * a.nbh + pos.bi) * a.nbw + pos.bj);
-        embed_blocks<B, false>(a, pos, id, lds, lds2);
-    }
+    constexpr bool KEY = false;
+#include "tmfwm_embed_pass_body.h"
 }
 
-// The key variant (a.key_out set): embed_kernel with embed_blocks<B, LIST, true>.  The body is
-// written out a second time: with both kernels calling one device function for it,
-// embed_kernel<8> compiled to 256 VGPRs and 56 bytes of scratch instead of 255 and none.
+// The key variant (a.key_out set): embed_kernel with embed_blocks<B, LIST, true>.
 template <int B, bool LIST = false>
 __global__ __launch_bounds__(64, kEmbedWaves<B>) void embed_key_kernel(EmbedArgs a)
 {
-    constexpr int L = Geo<B>::L, BPW = Geo<B>::BPW, TS = kEmbedTS<B>;
-    __shared__ __attribute__((aligned(16))) float lds_all[BPW * TS + kHiPad<B> + kLds2Floats<B>];
-    float *lds = lds_all, *lds2 = lds_all + BPW * TS + kHiPad<B>;
-    if constexpr (LIST) {
-        // grid-stride over the slow list's segments (their lengths are known on the device only)
-        const uint32_t per_frame = (uint32_t)a.nbh * (uint32_t)a.nbw, rows = (uint32_t)a.nframes * (uint32_t)a.nbh;
-        const int g = (threadIdx.x & 63) / L;
-        for (uint32_t s = blockIdx.x; s < kListShards; s += gridDim.x) {
-            const uint32_t n = a.slow_shards[s * kShardStride], base = shard_base(s, rows, (uint32_t)a.nbw);
-            if (n != 0 && (threadIdx.x & 63) == 0) atomicAdd(a.slow_count, n);
-            for (uint32_t t0 = 0; t0 < n; t0 += BPW) {
-                StripPos pos;
-                pos.valid = t0 + g < n;
-                const uint32_t id = pos.valid ? a.slow_list[base + t0 + g] : 0u;
-                pos.frame = id / per_frame;
-                const uint32_t rem = id % per_frame;
-                pos.bi = (int)(rem / (uint32_t)a.nbw);
-                pos.bj = (int)(rem % (uint32_t)a.nbw);
-                embed_blocks<B, true, true>(a, pos, id, lds, lds2);
-                __syncthreads();  // the LDS tiles are reused by the next listed blocks
-            }
-        }
-    } else {
-        const StripPos pos = strip_pos<B>(a.strips_per_row, a.nbw);
-        const uint32_t id = (uint32_t)(((int64_t)blockIdx.y * a.nbh + pos.bi) * a.nbw + pos.bj);
-        embed_blocks<B, false, true>(a, pos, id, lds, lds2);
-    }
+    constexpr bool KEY = true;
+#include "tmfwm_embed_pass_body.h"
 }
 
 }  // namespace tmf

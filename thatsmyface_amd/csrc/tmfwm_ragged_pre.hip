@@ -17,28 +17,35 @@
 namespace tmf {
 
 #if TMF_RAGGED_PRE_PART & 1
-// One wave per strip on the flat grid, as embed_ragged_kernel: embed_rank1_blocks on the frame's
-// one-frame view.  A block it leaves goes to the frame's shard of its row (TMFWM_ROUTE_RANK1) or
-// to the dgesdd-route list (TMFWM_ROUTE_RANK1_REFERENCE), by its chunk-relative id either way.
+// One wave per strip on the flat grid, as embed_ragged_kernel: the pre-pass (tmfwm_rank1_body.h)
+// on the frame's one-frame view.  A block it leaves goes to the frame's shard of its row
+// (TMFWM_ROUTE_RANK1) or to the dgesdd-route list (TMFWM_ROUTE_RANK1_REFERENCE), by its
+// chunk-relative id either way.
 template <int B>
-__global__ __launch_bounds__(64, kRank1Waves<B>) void embed_rank1_ragged_kernel(RaggedRank1Args r)
+__global__ __launch_bounds__(64, kRank1Waves<B>) void embed_rank1_ragged_kernel(RaggedRank1Args rag)
 {
+    constexpr int L = Geo<B>::L, R = Geo<B>::R, LD = B + 1, NW = Geo<B>::NW;
+    constexpr double u53 = 1.1102230246251565e-16;  // 2^-53
+    constexpr float u24 = 5.9604644775390625e-08f;  // 2^-24
     __shared__ float lds[kRank1LdsFloats<B>];
     __shared__ uint32_t pix[kRank1PixWords<B>][64];
-    RaggedFrameK *f = ragged_wave_frame(r);
-    const EmbedArgs a = ragged_embed_view(r, f);
+    const int lane = threadIdx.x & 63, g = lane / L, q = lane % L;
+    float *tile = lds + g * B * LD;
+    RaggedFrameK *f = ragged_wave_frame(rag);
+    const EmbedArgs a = ragged_embed_view(rag, f);
     uint32_t id;
     const StripPos pos = ragged_strip_pos<B>(f, id);
-    embed_rank1_blocks<B>(a, pos, lds, pix, [&] {
-        if (r.slow_list) {
-            const RaggedShardsK *sh = ragged_shards_const(r.shards) + (f - ragged_const(r.frames));
-            const uint32_t n = sh->n, k = (uint32_t)pos.bi % n;
-            r.slow_list[ragged_seg_base(f->block0, (uint32_t)f->nbh, (uint32_t)f->nbw, n, k) +
-                        atomicAdd(r.slow_shards + (sh->sh0 + k) * kShardStride, 1u)] = id;
-        } else {
-            r.fb_list[atomicAdd(r.fb_count, 1u)] = id;
-        }
-    });
+#define TMF_RANK1_LEFT                                                                                         \
+    if (rag.slow_list) {                                                                                       \
+        const RaggedShardsK *sh = ragged_shards_const(rag.shards) + (f - ragged_const(rag.frames));            \
+        const uint32_t n = sh->n, k = (uint32_t)pos.bi % n;                                                    \
+        rag.slow_list[ragged_seg_base(f->block0, (uint32_t)f->nbh, (uint32_t)f->nbw, n, k) +                   \
+                      atomicAdd(rag.slow_shards + (sh->sh0 + k) * kShardStride, 1u)] = id;                     \
+    } else {                                                                                                   \
+        rag.fb_list[atomicAdd(rag.fb_count, 1u)] = id;                                                         \
+    }
+#include "tmfwm_rank1_body.h"
+#undef TMF_RANK1_LEFT
 }
 
 template <int B>

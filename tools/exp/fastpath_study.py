@@ -42,7 +42,7 @@ import k_corpus as KC  # noqa: E402
 U32 = 2.0**-24
 EPS = 2.0**-53
 # LAPACK's two measured constants of the rank-1 pre-pass, in units of 2^-53 s1 (the kernel's
-# kRank1ResidUnits / kRank1PairUnits, csrc/tmfwm_rank1.hip; tools/exp/lapack_bounds.py measures them)
+# kRank1ResidUnits / kRank1PairUnits, csrc/tmfwm_rank1.h; tools/exp/lapack_bounds.py measures them)
 RESID_UNITS = KC.RESID_UNITS
 PAIR_UNITS = KC.PAIR_UNITS
 GATE_EPS_UV = 2.0**-30  # the pre-pass refuses a block whose top pair is known no better than this
@@ -121,7 +121,7 @@ def certify(cov, tile, b, alpha=0.1, K_A=1024.0, K_uv=1024.0, kappa=2.0, L=16, r
 
 
 def certify_rank1(cov, tile, b, alpha=0.1, iters=4, scale=1.0, per_block=False, route_check=True):
-    """The shipped pre-pass's bound (csrc/tmfwm_rank1.hip, round 6) restated in numpy: the top
+    """The shipped pre-pass's bound (csrc/tmfwm_rank1.h, tmfwm_rank1_body.h, round 6) restated in numpy: the top
     pair from `iters` f64 power steps on D^T D from the column-norm vector with the a-posteriori
     angle (Kato-Temple margins, Davis-Kahan) plus LAPACK's 1024 2^-53 s1 / (s1 - s2); dM in rank-one
     form (alpha' G + beta' P + gamma'); the IDCT roundings through |M_fast| <= G + |c| P; bytes at

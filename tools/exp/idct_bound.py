@@ -1,5 +1,5 @@
 """Rigorous first-order rounding bound of the f32 IDCT (pocketfft's DCT-III, ortho) at every slider
-length: the input to the rank-1 pre-pass's eps_Y (csrc/tmfwm_rank1.hip).
+length: the input to the rank-1 pre-pass's eps_Y (csrc/tmfwm_rank1_body.h).
 
 The device and the reference compute Y = IDCT_fl(M) with pocketfft's op sequence in f32
 (csrc/tmfwm_device.h dct::dct3 / rfft_forward / radf*; the op order is the parity contract).  This

@@ -1,4 +1,4 @@
-"""The rank-1 pre-pass's two LAPACK constants at scale (csrc/tmfwm_rank1.hip header).
+"""The rank-1 pre-pass's two LAPACK constants at scale (csrc/tmfwm_rank1.h).
 
 The pre-pass bounds |M_ref - M_fast| assuming
   (1) LAPACK's residual |(U S V^T)_ij - D_ij| <= 8192 units of 2^-53 sigma_1 (gamma' = 2^-40 s1), and
