@@ -20,6 +20,7 @@ Run:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_golden.py            (ca
       PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_golden.py --blocks   (cases_blocks.npz, meta_blocks.json)
       PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_golden.py --alpha    (cases_alpha.npz, meta_alpha.json)
       PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_golden.py --helpers  (helpers.npz, meta_helpers.json)
+      PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_golden.py --uploads  (cases_uploads.npz, meta_uploads.json)
 """
 from __future__ import annotations
 
@@ -365,9 +366,99 @@ def main_helpers() -> None:
     print("wrote helpers.npz:", sorted(out))
 
 
+UPLOAD_BLOCKS = (4, 6, 8, 10, 12, 14, 16)
+UPLOAD_ALPHA = 0.1
+UPLOAD_CLASSES = ("jpeg75", "noise3", "blur", "shift", "other")
+# cases_uploads.npz stays under 1 MB: the classes a numpy / Pillow filter makes (the GPU tests compare
+# those with the oracle at every size anyway) are left out at the largest sizes first
+UPLOAD_DROPPED = {16: ("blur", "shift"), 14: ("blur", "shift"), 12: ("shift",)}
+
+
+def main_uploads() -> None:
+    """cases_uploads.npz + meta_uploads.json: extract_watermark on uploads that are NOT the embed
+    output -- the reference's own embed output re-saved as a real JPEG (quality 75, decoded here so
+    that no test decodes one), with +-3 noise, blurred, shifted, or swapped for an unrelated
+    photograph (tests/upload_classes.py) -- on a camera-like and a QR cover of (5b+3) x (9b+5)
+    pixels at every slider size; per size also an original 7 rows and 11 columns larger than the
+    upload (the reference slices it), an RGBA upload with a random alpha plane, and a mode-"L"
+    original.  An array used by several cases (a cover under its five uploads) is stored once;
+    meta["cases"][name]["upload" / "original" / "extract"] name the arrays."""
+    import PIL
+    import scipy
+    from PIL import Image
+
+    tests = os.path.dirname(HERE)
+    for p in (os.path.dirname(tests), tests):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import upload_classes as UC
+    from lapack_path import photo_cover
+
+    W = _import_reference()
+    out: dict[str, np.ndarray] = {}
+    meta: dict = {"generator": "tests/golden/gen_golden.py --uploads",
+                  "reference": "/root/reference/modules/watermarking.py (embed_watermark :135, extract_watermark :224)",
+                  "numpy": np.__version__, "scipy": scipy.__version__, "pillow": PIL.__version__, "alpha": UPLOAD_ALPHA, "cases": {}}
+
+    def record(name, b, up_key, up_img, or_key, or_img):
+        settings = {"block_size": b, "alpha": UPLOAD_ALPHA}
+        ext = np.asarray(W.extract_watermark(up_img, or_img, settings))
+        for k, img in ((up_key, up_img), (or_key, or_img)):
+            a = np.asarray(img)
+            assert k not in out or np.array_equal(out[k], a)
+            out[k] = a
+        out[f"{name}/extract"] = ext
+        meta["cases"][name] = {"block": b, "upload": up_key, "upload_mode": up_img.mode, "original": or_key,
+                               "original_mode": or_img.mode, "extract": f"{name}/extract", "sha_extract": sha(ext)}
+        print(name, up_img.mode, up_img.size, or_img.mode, or_img.size, ext.shape, flush=True)
+
+    for b in UPLOAD_BLOCKS:
+        H, Wd = 5 * b + 3, 9 * b + 5
+        settings = {"block_size": b, "alpha": UPLOAD_ALPHA}
+        tile = Image.fromarray(wmark("noise", H // b, Wd // b, 7000 + b), "L")
+        big = photo_cover(H + 7, Wd + 11, 7100 + b)
+        covers = {"photo": np.ascontiguousarray(big[:H, :Wd]), "qr": cover("qr", H, Wd, 7200 + b)}
+        embeds = {}
+        for ck, carr in covers.items():
+            cimg = Image.fromarray(carr, "RGB")
+            emb = np.asarray(W.embed_watermark(cimg, tile, False, settings))
+            embeds[ck] = emb
+            buf = io.BytesIO()
+            Image.fromarray(emb, "RGB").save(buf, format="JPEG", quality=75)
+            ups = {"jpeg75": np.asarray(Image.open(io.BytesIO(buf.getvalue())).convert("RGB")),
+                   "noise3": UC.noise3(emb, 7300 + b), "blur": UC.blur(emb), "shift": UC.shift(emb), "other": UC.other(emb, 7300 + b)}
+            for cls in UPLOAD_CLASSES:
+                if cls in UPLOAD_DROPPED.get(b, ()):
+                    continue
+                name = f"b{b}/{ck}/{cls}"
+                # the unrelated photograph is the same under both covers: stored once
+                record(name, b, f"b{b}/other" if cls == "other" else f"{name}/upload", Image.fromarray(np.ascontiguousarray(ups[cls]), "RGB"), f"b{b}/{ck}/cover", cimg)
+        emb = embeds["photo"]
+        # an original larger than the upload: the reference reads its top-left H x W pixels
+        record(f"b{b}/photo/larger_original", b, f"b{b}/photo/noise3/upload", Image.fromarray(UC.noise3(emb, 7300 + b), "RGB"),
+               f"b{b}/photo/big_cover", Image.fromarray(big, "RGB"))
+        # an RGBA upload: convert("RGB") drops the alpha plane
+        a = np.random.default_rng(7400 + b).integers(0, 256, (H, Wd, 1), dtype=np.uint8)
+        record(f"b{b}/photo/rgba_upload", b, f"b{b}/photo/rgba_upload/upload",
+               Image.fromarray(np.concatenate([UC.blur(emb), a], -1), "RGBA"), f"b{b}/photo/cover", Image.fromarray(covers["photo"], "RGB"))
+        # a mode-"L" original: embed converts it to RGB, and so does extract
+        limg = Image.fromarray(covers["photo"], "RGB").convert("L")
+        lemb = np.asarray(W.embed_watermark(limg, tile, False, settings))
+        record(f"b{b}/photo/l_original", b, f"b{b}/photo/l_original/upload", Image.fromarray(UC.noise3(lemb, 7500 + b), "RGB"),
+               f"b{b}/photo/l_cover", limg)
+    np.savez_compressed(os.path.join(HERE, "cases_uploads.npz"), **out)
+    with open(os.path.join(HERE, "cases_uploads.npz"), "rb") as f:
+        meta["sha256_npz"] = hashlib.sha256(f.read()).hexdigest()
+    with open(os.path.join(HERE, "meta_uploads.json"), "w") as f:
+        json.dump(meta, f, indent=1, sort_keys=True)
+    print("wrote cases_uploads.npz", os.path.getsize(os.path.join(HERE, "cases_uploads.npz")), "bytes, meta_uploads.json")
+
+
 if __name__ == "__main__":
     if "--helpers" in sys.argv[1:]:
         main_helpers()
+    elif "--uploads" in sys.argv[1:]:
+        main_uploads()
     elif "--blocks" in sys.argv[1:]:
         main_blocks()
     elif "--alpha" in sys.argv[1:]:
