@@ -447,6 +447,35 @@ int tmfwm_embed_ragged_rank1(const tmfwm_embed_frame *frames, int64_t n_frames, 
 int tmfwm_embed_key_ragged_rank1(const tmfwm_embed_key_frame *frames, int64_t n_frames, int32_t block, double alpha,
                                  int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
 
+/*
+ * The ragged calls with one alpha per frame (added within ABI 10; the version number is unchanged
+ * and the calls above keep their signatures and behaviour): uploads of several sessions, each
+ * with its own strength setting, or one cover at several strengths, in one set of launches.
+ * `alphas` is n_frames doubles in host memory whatever mem_kind says, copied with the descriptors
+ * before the call returns; NULL with n_frames > 0 is TMFWM_ERR_INVALID.  Every entry is checked
+ * before the device is touched, whether or not its frame has a block -- finite for the embeds,
+ * finite and non-zero for the extracts -- and the message names the frame index.
+ *
+ * Frame i's output bytes are those of the uniform call on that frame alone with alpha = alphas[i]
+ * (the key bits likewise; they do not depend on alpha), hence tmfwm_embed_route's /
+ * tmfwm_extract_route's / tmfwm_extract_keyed's on that frame; the extracts divide by
+ * f32(alphas[i]).  Descriptors, memory kinds, the overlap rules, frames without a block, chunking,
+ * the count, tmfwm_last_list_pass_blocks() and the non-convergence report are the uniform
+ * siblings'.  The embeds take all four routes, as tmfwm_embed_ragged_rank1 /
+ * tmfwm_embed_key_ragged_rank1 do (the key call composed on the rank-1 routes as there); the
+ * extracts take TMFWM_ROUTE_HYBRID and TMFWM_ROUTE_REFERENCE; the keyed extract takes 3- or 4-byte
+ * pixels as tmfwm_extract_keyed_ragged_px does.
+ */
+int tmfwm_embed_ragged_alphas(const tmfwm_embed_frame *frames, const double *alphas, int64_t n_frames, int32_t block,
+                              int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
+int tmfwm_embed_key_ragged_alphas(const tmfwm_embed_key_frame *frames, const double *alphas, int64_t n_frames, int32_t block,
+                                  int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
+int tmfwm_extract_ragged_alphas(const tmfwm_extract_frame *frames, const double *alphas, int64_t n_frames, int32_t block,
+                                int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks);
+int tmfwm_extract_keyed_ragged_alphas(const tmfwm_keyed_frame *frames, const double *alphas, int64_t n_frames, int32_t block,
+                                      int32_t pixel_bytes, int32_t mem_kind, void *hip_stream, int32_t route,
+                                      int64_t *n_lapack_blocks);
+
 /* tmfwm_extract_route with a pixel layout and frame stride per input image (ABI 8). */
 int tmfwm_extract_px(const uint8_t *wm_rgb, int32_t wm_pixel_bytes, int64_t wm_frame_stride, const uint8_t *orig_rgb,
                      int32_t orig_pixel_bytes, int64_t orig_frame_stride, int64_t n_frames, int32_t height, int32_t width,

@@ -6,6 +6,7 @@ CPU fallback: if the library or a GPU is missing every call raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import importlib.util
 import os
@@ -126,6 +127,11 @@ SIGNATURES = {
     "tmfwm_embed_key_ragged": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _VP, _I32, _VP]),
     "tmfwm_embed_ragged_rank1": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _VP, _I32, _VP]),
     "tmfwm_embed_key_ragged_rank1": (ctypes.c_int, [_VP, _I64, _I32, _D, _I32, _VP, _I32, _VP]),
+    # the ragged calls with one alpha per frame (frames, alphas: n_frames host doubles, ...)
+    "tmfwm_embed_ragged_alphas": (ctypes.c_int, [_VP, _VP, _I64, _I32, _I32, _VP, _I32, _VP]),
+    "tmfwm_embed_key_ragged_alphas": (ctypes.c_int, [_VP, _VP, _I64, _I32, _I32, _VP, _I32, _VP]),
+    "tmfwm_extract_ragged_alphas": (ctypes.c_int, [_VP, _VP, _I64, _I32, _I32, _VP, _I32, _VP]),
+    "tmfwm_extract_keyed_ragged_alphas": (ctypes.c_int, [_VP, _VP, _I64, _I32, _I32, _I32, _VP, _I32, _VP]),
     # the keyed calls with a pixel layout (3 or 4 bytes per pixel)
     "tmfwm_sigma1_map_px": (ctypes.c_int, [_VP, _I32, _I64, _I64, _I32, _I32, _I32, _VP, _I32, _VP, _I32, _VP]),
     "tmfwm_extract_keyed_px": (ctypes.c_int, [_VP, _I32, _I64, _I64, _I32, _I32, _VP, _I64, _I32, _D, _VP, _I32, _VP, _I32, _VP]),
@@ -205,6 +211,36 @@ def load():
                 raise ImportError(f"libtmfwm ABI {v} != expected {ABI_VERSION}")
             _lib = L
     return _lib
+
+
+def open_build(path: str):
+    """Another build of the library (same ABI), loaded and typed beside the one `load()` returns:
+    for `using()`.  An older build may lack the newer entries; those stay untyped and uncalled."""
+    load()  # the shared HIP runtime first
+    other = ctypes.CDLL(path)
+    for name, (res, args) in SIGNATURES.items():
+        if hasattr(other, name):
+            fn = getattr(other, name)
+            fn.restype = res
+            fn.argtypes = args
+    v = other.tmfwm_abi_version()
+    if v != ABI_VERSION:
+        raise ImportError(f"{path}: libtmfwm ABI {v} != expected {ABI_VERSION}")
+    return other
+
+
+@contextlib.contextmanager
+def using(build):
+    """Within the block every call of this process's binding goes to `build` (from `open_build`):
+    two builds timed against each other in alternating windows of one run (tools/ragged_bench.py).
+    Not for concurrent use from several threads."""
+    global _lib
+    mine = load()
+    _lib = build
+    try:
+        yield build
+    finally:
+        _lib = mine
 
 
 def last_error() -> str:

@@ -260,6 +260,26 @@ def _ragged_route(route) -> int:
     return code
 
 
+def _ragged_alphas(alpha, n: int, what: str = "frames"):
+    """The alpha of a ragged call: a number -- None, the uniform entry takes float(alpha) -- or a
+    sequence of one alpha per frame -- a C array of n doubles for the *_ragged_alphas entry.  A
+    sequence of another length is a ValueError, raised before anything about the tensors or the
+    device is looked at."""
+    import ctypes
+    import numbers
+
+    # a number in any dress (a Python or numpy scalar, a 0-d array or tensor) is the uniform call's
+    if isinstance(alpha, numbers.Real) or getattr(alpha, "ndim", None) == 0:
+        return None
+    try:
+        vals = [float(a) for a in alpha]  # a list, tuple, 1-d array or tensor, or any other iterable
+    except TypeError:
+        raise TypeError(f"alpha must be a number or a sequence of one number per frame, got {type(alpha).__name__}") from None
+    if len(vals) != n:
+        raise ValueError(f"{len(vals)} alphas for {n} {what}: alpha is one number, or one per frame")
+    return (ctypes.c_double * max(n, 1))(*vals)
+
+
 def _embed_ragged_args(frames, tiles, block, route, out, rank1_routes: bool = False):
     """embed_ragged's checks and output views: (frames, tiles, out, device, route code)."""
     if block not in SUPPORTED_BLOCK_SIZES:
@@ -293,6 +313,8 @@ def embed_ragged_rank1(frames, tiles, block: int = 8, alpha: float = 0.1, out=No
     stats["list_pass_blocks"] is what the pre-pass left to the list pass on "rank1"."""
     import ctypes
 
+    frames = list(frames)
+    alphas = _ragged_alphas(alpha, len(frames))
     frames, tiles, out, dev, code = _embed_ragged_args(frames, tiles, block, route, out, rank1_routes=True)
     desc = (_lib.EmbedFrame * max(len(frames), 1))()
     for i, (f, t, o) in enumerate(zip(frames, tiles, out)):
@@ -301,8 +323,13 @@ def embed_ragged_rank1(frames, tiles, block: int = 8, alpha: float = 0.1, out=No
     L = _lib.load()
     if frames:
         with torch.cuda.device(dev):
-            _lib.check(L.tmfwm_embed_ragged_rank1(ctypes.addressof(desc), len(frames), block, float(alpha), _lib.MEM_DEVICE,
-                                                  _stream(stream), code, ptr), "embed_ragged_rank1")
+            if alphas is None:
+                rc = L.tmfwm_embed_ragged_rank1(ctypes.addressof(desc), len(frames), block, float(alpha), _lib.MEM_DEVICE,
+                                                _stream(stream), code, ptr)
+            else:
+                rc = L.tmfwm_embed_ragged_alphas(ctypes.addressof(desc), ctypes.addressof(alphas), len(frames), block,
+                                                 _lib.MEM_DEVICE, _stream(stream), code, ptr)
+            _lib.check(rc, "embed_ragged_rank1")
     if stats is not None:
         stats["lapack_blocks"] = int(cnt.value)
         stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks()) if frames else 0
@@ -317,9 +344,14 @@ def embed_ragged(frames, tiles, block: int = 8, alpha: float = 0.1, out=None, st
     allocation (or `out`, a sequence of tensors shaped like the frames); output i is the bytes
     of embed_batch(frames[i][None], tiles[i], ...)[0].  A frame smaller than a block gets its
     colour round trip.  stats and route ("hybrid" / "reference") as embed_batch's; no list pass
-    runs, so "list_pass_blocks" is 0."""
+    runs, so "list_pass_blocks" is 0.  alpha is one number, or a sequence of len(frames) numbers,
+    one per frame (tmfwm_embed_ragged_alphas; here and in the other ragged calls that take an
+    alpha): output i is then embed_batch's at alpha[i], and a sequence of another length is a
+    ValueError before any device work."""
     import ctypes
 
+    frames = list(frames)
+    alphas = _ragged_alphas(alpha, len(frames))
     frames, tiles, out, dev, code = _embed_ragged_args(frames, tiles, block, route, out)
     desc = (_lib.EmbedFrame * max(len(frames), 1))()
     for i, (f, t, o) in enumerate(zip(frames, tiles, out)):
@@ -328,8 +360,13 @@ def embed_ragged(frames, tiles, block: int = 8, alpha: float = 0.1, out=None, st
     L = _lib.load()
     if frames:
         with torch.cuda.device(dev):
-            _lib.check(L.tmfwm_embed_ragged(ctypes.addressof(desc), len(frames), block, float(alpha), _lib.MEM_DEVICE,
-                                            _stream(stream), code, ptr), "embed_ragged")
+            if alphas is None:
+                rc = L.tmfwm_embed_ragged(ctypes.addressof(desc), len(frames), block, float(alpha), _lib.MEM_DEVICE,
+                                          _stream(stream), code, ptr)
+            else:
+                rc = L.tmfwm_embed_ragged_alphas(ctypes.addressof(desc), ctypes.addressof(alphas), len(frames), block,
+                                                 _lib.MEM_DEVICE, _stream(stream), code, ptr)
+            _lib.check(rc, "embed_ragged")
     if stats is not None:
         stats["lapack_blocks"] = int(cnt.value)
         stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks()) if frames else 0
@@ -344,6 +381,8 @@ def extract_ragged(wframes, oframes, block: int = 8, alpha: float = 0.1, out=Non
     `out`); tile i is the bytes of extract_batch(wframes[i][None], oframes[i][None], ...)[0]."""
     import ctypes
 
+    wframes = list(wframes)
+    alphas = _ragged_alphas(alpha, len(wframes))
     if block not in SUPPORTED_BLOCK_SIZES:
         raise NotImplementedError(f"block {block}")
     code = _ragged_route(route)
@@ -372,8 +411,13 @@ def extract_ragged(wframes, oframes, block: int = 8, alpha: float = 0.1, out=Non
     L = _lib.load()
     if wframes:
         with torch.cuda.device(dev):
-            _lib.check(L.tmfwm_extract_ragged(ctypes.addressof(desc), len(wframes), block, float(alpha), _lib.MEM_DEVICE,
-                                              _stream(stream), code, ptr), "extract_ragged")
+            if alphas is None:
+                rc = L.tmfwm_extract_ragged(ctypes.addressof(desc), len(wframes), block, float(alpha), _lib.MEM_DEVICE,
+                                            _stream(stream), code, ptr)
+            else:
+                rc = L.tmfwm_extract_ragged_alphas(ctypes.addressof(desc), ctypes.addressof(alphas), len(wframes), block,
+                                                   _lib.MEM_DEVICE, _stream(stream), code, ptr)
+            _lib.check(rc, "extract_ragged")
     if stats is not None:
         stats["lapack_blocks"] = int(cnt.value)
         stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks()) if wframes else 0
@@ -439,6 +483,8 @@ def embed_with_key_ragged(frames, tiles, block: int = 8, alpha: float = 0.1, out
     embed_ragged's."""
     import ctypes
 
+    frames = list(frames)
+    alphas = _ragged_alphas(alpha, len(frames))
     frames, tiles, out, dev, code = _embed_ragged_args(frames, tiles, block, route, out)
     shapes = [(f.shape[0] // block, f.shape[1] // block) for f in frames]
     if key_out is None:  # float32 views of one uint8 allocation: its pieces start on 16-byte boundaries
@@ -453,8 +499,13 @@ def embed_with_key_ragged(frames, tiles, block: int = 8, alpha: float = 0.1, out
     L = _lib.load()
     if frames:
         with torch.cuda.device(dev):
-            _lib.check(L.tmfwm_embed_key_ragged(ctypes.addressof(desc), len(frames), block, float(alpha), _lib.MEM_DEVICE,
-                                                _stream(stream), code, ptr), "embed_with_key_ragged")
+            if alphas is None:
+                rc = L.tmfwm_embed_key_ragged(ctypes.addressof(desc), len(frames), block, float(alpha), _lib.MEM_DEVICE,
+                                              _stream(stream), code, ptr)
+            else:
+                rc = L.tmfwm_embed_key_ragged_alphas(ctypes.addressof(desc), ctypes.addressof(alphas), len(frames), block,
+                                                     _lib.MEM_DEVICE, _stream(stream), code, ptr)
+            _lib.check(rc, "embed_with_key_ragged")
     if stats is not None:
         stats["lapack_blocks"] = int(cnt.value)
         stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks()) if frames else 0
@@ -469,6 +520,8 @@ def embed_with_key_ragged_rank1(frames, tiles, block: int = 8, alpha: float = 0.
     Arguments, checks and the return value are embed_with_key_ragged's."""
     import ctypes
 
+    frames = list(frames)
+    alphas = _ragged_alphas(alpha, len(frames))
     frames, tiles, out, dev, code = _embed_ragged_args(frames, tiles, block, route, out, rank1_routes=True)
     shapes = [(f.shape[0] // block, f.shape[1] // block) for f in frames]
     if key_out is None:  # float32 views of one uint8 allocation: its pieces start on 16-byte boundaries
@@ -483,8 +536,13 @@ def embed_with_key_ragged_rank1(frames, tiles, block: int = 8, alpha: float = 0.
     L = _lib.load()
     if frames:
         with torch.cuda.device(dev):
-            _lib.check(L.tmfwm_embed_key_ragged_rank1(ctypes.addressof(desc), len(frames), block, float(alpha), _lib.MEM_DEVICE,
-                                                      _stream(stream), code, ptr), "embed_with_key_ragged_rank1")
+            if alphas is None:
+                rc = L.tmfwm_embed_key_ragged_rank1(ctypes.addressof(desc), len(frames), block, float(alpha), _lib.MEM_DEVICE,
+                                                    _stream(stream), code, ptr)
+            else:
+                rc = L.tmfwm_embed_key_ragged_alphas(ctypes.addressof(desc), ctypes.addressof(alphas), len(frames), block,
+                                                     _lib.MEM_DEVICE, _stream(stream), code, ptr)
+            _lib.check(rc, "embed_with_key_ragged_rank1")
     if stats is not None:
         stats["lapack_blocks"] = int(cnt.value)
         stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks()) if frames else 0
@@ -506,6 +564,7 @@ def extract_keyed_ragged(wframes, keys, block: int = 8, alpha: float = 0.1, out=
         raise NotImplementedError(f"block {block}")
     code = _ragged_route(route)
     wframes, keys = list(wframes), list(keys)
+    alphas = _ragged_alphas(alpha, len(wframes))
     if len(keys) != len(wframes):
         raise ValueError(f"{len(keys)} keys for {len(wframes)} frames")
     # what a key is, and whether it fits its frame, before any tensor's device is looked at
@@ -532,8 +591,13 @@ def extract_keyed_ragged(wframes, keys, block: int = 8, alpha: float = 0.1, out=
     L = _lib.load()
     if wframes:
         with torch.cuda.device(dev):
-            _lib.check(L.tmfwm_extract_keyed_ragged_px(ctypes.addressof(desc), len(wframes), block, float(alpha), px,
-                                                       _lib.MEM_DEVICE, _stream(stream), code, ptr), "extract_keyed_ragged")
+            if alphas is None:
+                rc = L.tmfwm_extract_keyed_ragged_px(ctypes.addressof(desc), len(wframes), block, float(alpha), px,
+                                                     _lib.MEM_DEVICE, _stream(stream), code, ptr)
+            else:
+                rc = L.tmfwm_extract_keyed_ragged_alphas(ctypes.addressof(desc), ctypes.addressof(alphas), len(wframes), block, px,
+                                                         _lib.MEM_DEVICE, _stream(stream), code, ptr)
+            _lib.check(rc, "extract_keyed_ragged")
     if stats is not None:
         stats["lapack_blocks"] = int(cnt.value)
         stats["list_pass_blocks"] = int(L.tmfwm_last_list_pass_blocks()) if wframes else 0

@@ -1565,6 +1565,7 @@ struct RFrame {
     int32_t H, W;
     uint8_t *out2 = nullptr;  // RKind::EmbedKey only
     int32_t px = 3;           // bytes per pixel of in0 (4: the keyed *_ragged_px calls, one layout per call)
+    double alpha = 0.0;       // the *_ragged_alphas calls: the frame's own alpha
     int64_t pixel_bytes() const { return (int64_t)H * W * px; }
     int64_t tile_bytes(int b) const { return (int64_t)(H / b) * (W / b); }
     // the bytes behind in1 and out
@@ -1597,6 +1598,18 @@ int check_ragged_call(const void *frames, int64_t n, int32_t block, double alpha
     if (mem_kind != TMFWM_MEM_HOST && mem_kind != TMFWM_MEM_DEVICE) return fail(TMFWM_ERR_INVALID, "mem_kind %d", mem_kind);
     if (kind != RKind::Map && (extract ? (!std::isfinite(alpha) || alpha == 0.0) : !std::isfinite(alpha)))  // the map takes no alpha
         return fail(TMFWM_ERR_INVALID, extract ? "alpha must be finite and non-zero" : "alpha is not finite");
+    return 0;
+}
+
+// the *_ragged_alphas calls: n doubles in host memory, every one checked whether or not its frame has a block
+int check_ragged_alphas(const double *alphas, int64_t n, RKind kind)
+{
+    const bool extract = kind == RKind::Extract || kind == RKind::Keyed;
+    if (n > 0 && !alphas) return fail(TMFWM_ERR_INVALID, "alphas is NULL");
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(alphas[i]) || (extract && alphas[i] == 0.0))
+            return fail(TMFWM_ERR_INVALID, extract ? "frame %lld: alpha must be finite and non-zero" : "frame %lld: alpha is not finite",
+                        (long long)i);
     return 0;
 }
 
@@ -1745,7 +1758,8 @@ bool rank1_route(int route) { return route == TMFWM_ROUTE_RANK1 || route == TMFW
 
 // What run_ragged takes: the frame table of the frames that have work, with chunk-relative
 // prefixes, the chunks, and the table's side tables -- RKind::EmbedKey: each entry's key output;
-// TMFWM_ROUTE_RANK1: each entry's list-pass shards, relative to its chunk as the ids are.
+// TMFWM_ROUTE_RANK1: each entry's list-pass shards, relative to its chunk as the ids are; the
+// *_ragged_alphas calls: each entry's alpha.
 struct RaggedPlan {
     RKind kind;
     int route;
@@ -1753,9 +1767,10 @@ struct RaggedPlan {
     std::vector<RaggedChunk> chunks;
     std::vector<float *> keys;
     std::vector<tmf::RaggedShards> shards;
+    std::vector<tmf::RaggedAlpha> alphas;
 };
 
-void plan_ragged(const std::vector<RFrame> &fr, int32_t block, RKind kind, int route, RaggedPlan &plan)
+void plan_ragged(const std::vector<RFrame> &fr, int32_t block, RKind kind, int route, RaggedPlan &plan, bool per_frame = false)
 {
     plan.kind = kind;
     plan.route = route;
@@ -1793,6 +1808,7 @@ void plan_ragged(const std::vector<RFrame> &fr, int32_t block, RKind kind, int r
         t.edge0 = c.edge;
         table.push_back(t);
         if (kind == RKind::EmbedKey) keys.push_back(reinterpret_cast<float *>(f.out2));
+        if (per_frame) plan.alphas.push_back(tmf::RaggedAlpha{f.alpha, (float)f.alpha, 0.0f});
         ++c.n;
         c.with_blocks += blocks > 0;
         c.waves += waves;
@@ -1806,9 +1822,12 @@ void plan_ragged(const std::vector<RFrame> &fr, int32_t block, RKind kind, int r
     }
 }
 
+size_t round16(size_t n) { return (n + 15) & ~size_t(15); }
+
 // Both passes of a ragged call over device-resident frames: the frame table uploaded, then the
 // chunks through two_pass, with the edge pass between a chunk's first pass and its fixup pass and
-// neither of the two for a chunk without a block.
+// neither of the two for a chunk without a block.  (alpha: the uniform calls'; a plan with an
+// alpha table runs the per-frame kernels, which do not read it)
 int run_ragged(int32_t block, double alpha, hipStream_t st, const Report &rep, const RaggedPlan &plan,
                int px = 3)  // px: the keyed kinds' bytes per pixel
 {
@@ -1822,14 +1841,19 @@ int run_ragged(int32_t block, double alpha, hipStream_t st, const Report &rep, c
     const bool pre = rank1_route(route) && kind == RKind::Embed && tmf::rank1_block(block);
     const bool list_pass = pre && route == TMFWM_ROUTE_RANK1;
     // the frame table and behind it the side tables -- the keys (RKind::EmbedKey), the list-pass
-    // shards (TMFWM_ROUTE_RANK1); empty otherwise -- in one upload
+    // shards (TMFWM_ROUTE_RANK1), the alphas (the *_ragged_alphas calls); empty otherwise -- in one upload
     const size_t fbytes = table.size() * sizeof(tmf::RaggedFrame), kbytes = keys.size() * sizeof(float *);
-    const size_t tbytes = fbytes + kbytes + plan.shards.size() * sizeof(tmf::RaggedShards);
+    const size_t sbytes = plan.shards.size() * sizeof(tmf::RaggedShards);
+    const size_t abase = round16(fbytes + kbytes + sbytes);  // (a chunk's kernels find its entries by their distance from its frames)
+    const size_t tbytes = abase + plan.alphas.size() * sizeof(tmf::RaggedAlpha);
+    if (tbytes > 0xFFFFFFFFull) return fail(TMFWM_ERR_INVALID, "too many frames for one call (%zu)", table.size());
     TableSlot slot;
     if (int rc = take_table(tbytes, stream_device(st), slot)) return rc;
     std::copy(table.begin(), table.end(), static_cast<tmf::RaggedFrame *>(slot.p));
     std::copy(keys.begin(), keys.end(), reinterpret_cast<float **>(static_cast<uint8_t *>(slot.p) + fbytes));
     std::copy(plan.shards.begin(), plan.shards.end(), reinterpret_cast<tmf::RaggedShards *>(static_cast<uint8_t *>(slot.p) + fbytes + kbytes));
+    std::copy(plan.alphas.begin(), plan.alphas.end(),
+              reinterpret_cast<tmf::RaggedAlpha *>(static_cast<uint8_t *>(slot.p) + abase));
     DevBuf dtable;
     int rc = dtable.alloc(tbytes, st, "frame table");
     if (rc == 0 && hipMemcpyAsync(dtable.p, slot.p, tbytes, hipMemcpyHostToDevice, st) != hipSuccess)
@@ -1838,6 +1862,10 @@ int run_ragged(int32_t block, double alpha, hipStream_t st, const Report &rep, c
     if (rc) return rc;
     std::vector<int64_t> blocks;
     for (const RaggedChunk &k : chunks) blocks.push_back(k.blocks);
+    // a chunk's slice of the alpha table, as its slice of the frame table: entry k.first, seen from frame k.first
+    auto alphas_off = [&](const RaggedChunk &k) -> uint32_t {
+        return plan.alphas.empty() ? 0u : (uint32_t)(abase + (size_t)k.first * sizeof(tmf::RaggedAlpha) - (size_t)k.first * sizeof(tmf::RaggedFrame));
+    };
     return two_pass(blocks, list_pass, true, st, rep, [&](int64_t c, const ChunkLists &w) -> int {
         const RaggedChunk &k = chunks[(size_t)c];
         if (pre) {  // the pre-pass (+ its list pass on TMFWM_ROUTE_RANK1), the edges, the dgesdd route
@@ -1847,6 +1875,7 @@ int run_ragged(int32_t block, double alpha, hipStream_t st, const Report &rep, c
             r.block = block;
             r.alpha = alpha;
             r.alpha32 = (float)alpha;
+            r.alphas_off = alphas_off(k);
             r.fb_list = w.fb_list;
             r.fb_count = w.fb_count;
             r.fb_bad = w.fb_bad;
@@ -1867,6 +1896,7 @@ int run_ragged(int32_t block, double alpha, hipStream_t st, const Report &rep, c
         r.block = block;
         r.alpha = alpha;
         r.alpha32 = (float)alpha;
+        r.alphas_off = alphas_off(k);
         r.fb_list = w.fb_list;  // no list pass in a ragged call
         r.fb_count = w.fb_count;
         r.fb_bad = w.fb_bad;
@@ -1891,10 +1921,8 @@ int run_ragged(int32_t block, double alpha, hipStream_t st, const Report &rep, c
     });
 }
 
-size_t round16(size_t n) { return (n + 15) & ~size_t(15); }
-
 int ragged_call(std::vector<RFrame> &fr, int32_t block, double alpha, RKind kind, int32_t mem_kind, void *hip_stream, int32_t route,
-                int64_t *n_lapack)
+                int64_t *n_lapack, bool per_frame = false)  // per_frame: RFrame::alpha of each frame instead of `alpha`
 {
     for (size_t i = 0; i < fr.size(); ++i)
         if (int rc = check_ragged_frame((int64_t)i, fr[i], block, kind)) return rc;
@@ -1913,7 +1941,7 @@ int ragged_call(std::vector<RFrame> &fr, int32_t block, double alpha, RKind kind
     };
     std::vector<Part> parts(composed ? 2 : 1);
     auto plan_parts = [&](const std::vector<RFrame> &v) {
-        if (!composed) return plan_ragged(v, block, kind, route, parts[0].plan);
+        if (!composed) return plan_ragged(v, block, kind, route, parts[0].plan, per_frame);
         std::vector<RFrame> emb(v), map(v);
         for (size_t i = 0; i < v.size(); ++i) {
             emb[i].out2 = nullptr;
@@ -1921,7 +1949,7 @@ int ragged_call(std::vector<RFrame> &fr, int32_t block, double alpha, RKind kind
             map[i].out = v[i].out2;
             map[i].out2 = nullptr;
         }
-        plan_ragged(emb, block, RKind::Embed, route, parts[0].plan);
+        plan_ragged(emb, block, RKind::Embed, route, parts[0].plan, per_frame);  // (the map takes no alpha)
         plan_ragged(map, block, RKind::Map, TMFWM_ROUTE_HYBRID, parts[1].plan);
     };
     int64_t total_n = 0, total_list = 0;
@@ -2183,6 +2211,66 @@ int tmfwm_extract_keyed_ragged(const tmfwm_keyed_frame *frames, int64_t n_frames
                                void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
 {
     return tmfwm_extract_keyed_ragged_px(frames, n_frames, block, alpha, TMFWM_PIX_RGB, mem_kind, hip_stream, route, n_lapack_blocks);
+}
+
+// one alpha per frame: the uniform calls' checks, then every alpha, then the same ragged_call with
+// each frame's alpha in its RFrame (copied, as the descriptors are, before the call returns); a
+// call without a frame is done once its arguments are checked
+int tmfwm_embed_ragged_alphas(const tmfwm_embed_frame *frames, const double *alphas, int64_t n_frames, int32_t block, int32_t mem_kind,
+                              void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    if (int rc = check_ragged_call(frames, n_frames, block, 1.0, RKind::Embed, mem_kind, route, n_lapack_blocks, true)) return rc;
+    if (int rc = check_ragged_alphas(alphas, n_frames, RKind::Embed)) return rc;
+    if (n_frames == 0) return 0;
+    std::vector<RFrame> fr((size_t)n_frames);
+    for (int64_t i = 0; i < n_frames; ++i) {
+        fr[(size_t)i] = RFrame{frames[i].rgb, frames[i].wm_tile, frames[i].out, frames[i].height, frames[i].width};
+        fr[(size_t)i].alpha = alphas[i];
+    }
+    return ragged_call(fr, block, 0.0, RKind::Embed, mem_kind, hip_stream, route, n_lapack_blocks, true);
+}
+
+int tmfwm_embed_key_ragged_alphas(const tmfwm_embed_key_frame *frames, const double *alphas, int64_t n_frames, int32_t block,
+                                  int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    if (int rc = check_ragged_call(frames, n_frames, block, 1.0, RKind::EmbedKey, mem_kind, route, n_lapack_blocks, true)) return rc;
+    if (int rc = check_ragged_alphas(alphas, n_frames, RKind::EmbedKey)) return rc;
+    if (n_frames == 0) return 0;
+    std::vector<RFrame> fr((size_t)n_frames);
+    for (int64_t i = 0; i < n_frames; ++i) {
+        fr[(size_t)i] = RFrame{frames[i].rgb, frames[i].wm_tile, frames[i].out, frames[i].height, frames[i].width,
+                               reinterpret_cast<uint8_t *>(frames[i].out_key)};
+        fr[(size_t)i].alpha = alphas[i];
+    }
+    return ragged_call(fr, block, 0.0, RKind::EmbedKey, mem_kind, hip_stream, route, n_lapack_blocks, true);
+}
+
+int tmfwm_extract_ragged_alphas(const tmfwm_extract_frame *frames, const double *alphas, int64_t n_frames, int32_t block,
+                                int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    if (int rc = check_ragged_call(frames, n_frames, block, 1.0, RKind::Extract, mem_kind, route, n_lapack_blocks)) return rc;
+    if (int rc = check_ragged_alphas(alphas, n_frames, RKind::Extract)) return rc;
+    if (n_frames == 0) return 0;
+    std::vector<RFrame> fr((size_t)n_frames);
+    for (int64_t i = 0; i < n_frames; ++i) {
+        fr[(size_t)i] = RFrame{frames[i].wm_rgb, frames[i].orig_rgb, frames[i].out_tile, frames[i].height, frames[i].width};
+        fr[(size_t)i].alpha = alphas[i];
+    }
+    return ragged_call(fr, block, 1.0, RKind::Extract, mem_kind, hip_stream, route, n_lapack_blocks, true);
+}
+
+int tmfwm_extract_keyed_ragged_alphas(const tmfwm_keyed_frame *frames, const double *alphas, int64_t n_frames, int32_t block,
+                                      int32_t pixel_bytes, int32_t mem_kind, void *hip_stream, int32_t route, int64_t *n_lapack_blocks)
+{
+    if (int rc = check_ragged_call(frames, n_frames, block, 1.0, RKind::Keyed, mem_kind, route, n_lapack_blocks)) return rc;
+    if (int rc = check_ragged_alphas(alphas, n_frames, RKind::Keyed)) return rc;
+    if (pixel_bytes != TMFWM_PIX_RGB && pixel_bytes != TMFWM_PIX_RGBX) return fail(TMFWM_ERR_INVALID, "pixel bytes %d (3 or 4)", pixel_bytes);
+    if (n_frames == 0) return 0;
+    std::vector<RFrame> fr((size_t)n_frames);
+    for (int64_t i = 0; i < n_frames; ++i)
+        fr[(size_t)i] = {frames[i].wm_rgb, reinterpret_cast<const uint8_t *>(frames[i].key), frames[i].out_tile, frames[i].height,
+                         frames[i].width,  nullptr, pixel_bytes, alphas[i]};
+    return ragged_call(fr, block, 1.0, RKind::Keyed, mem_kind, hip_stream, route, n_lapack_blocks, true);
 }
 
 int tmfwm_prepare_tiles_ragged(const tmfwm_tile_job *jobs, int64_t n_jobs, int32_t preserve_ratio, int32_t mem_kind,

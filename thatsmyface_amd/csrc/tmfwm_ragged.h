@@ -31,15 +31,30 @@ struct RaggedFrame {
 };
 static_assert(sizeof(RaggedFrame) == 64, "frame table entry");
 
+// One alpha per frame (tmfwm_*_ragged_alphas): a side table indexed as `frames` (device memory),
+// uploaded with the frame table of each chunk.  A kernel of the per-frame form reads its frame's
+// entry where the uniform form reads RaggedArgs::alpha / alpha32; everything else is shared.
+struct RaggedAlpha {
+    double alpha;   // embed
+    float alpha32;  // extract: f32(alpha)
+    float pad;
+};
+static_assert(sizeof(RaggedAlpha) == 16, "alpha table entry");
+
 struct RaggedArgs {
     const RaggedFrame *frames;  // the chunk's frames (device memory)
     int32_t nframes, block;
     double alpha;               // embed
     float alpha32;              // extract: f32(alpha), as ExtractArgs
+    uint32_t alphas_off;        // the per-frame form: the chunk's RaggedAlpha entries lie this many bytes behind `frames` (they are
+                                // uploaded with the frame table), and the dispatchers take the *_alphas kernels; 0: alpha / alpha32.
+                                // (In the struct's padding: the uniform kernels' arguments are where they were.)
     uint32_t *fb_list;          // the dgesdd-route list, ids relative to the chunk, as EmbedArgs / ExtractArgs
     uint32_t *fb_count;
     uint32_t *fb_bad;
 };
+
+static_assert(sizeof(RaggedArgs) == 56, "the uniform kernels' argument layout");
 
 // embed with key (tmfwm_embed_key.h): frame i's nbh x nbw f32 key output at keys[i] (device
 // memory, indexed as `frames`; 4-byte aligned) -- a side table and an argument struct of this call
@@ -162,6 +177,44 @@ template <int B>
 hipError_t extract_keyed_ragged_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
                                         hipStream_t st, int px);
 
+// The per-frame form (RaggedArgs::alphas_off set): the same sources compiled with
+// -DTMF_RAGGED_ALPHAS=1 into objects of their own (the Makefile's ALPHA_OBJS), whose kernels and
+// launchers carry _alphas in their names -- embed_ragged_alphas_kernel<b> beside
+// embed_ragged_kernel<b>, as the px4 kernels stand beside the 3-byte ones.  No uniform kernel
+// shares a translation unit with a new one, so its code is the parent's: the inliner counts a
+// function's call sites per unit, and a second kernel calling embed_blocks<b> costs
+// embed_ragged_kernel<6> a wave per SIMD (profiles/ragged_alphas).  The map takes no alpha.
+#ifndef TMF_RAGGED_ALPHAS
+#define TMF_RAGGED_ALPHAS 0
+#endif
+#if TMF_RAGGED_ALPHAS
+#define TMF_RAGGED_NAME(stem, rest) stem##_alphas##rest
+#else
+#define TMF_RAGGED_NAME(stem, rest) stem##rest
+#endif
+template <int B>
+hipError_t embed_ragged_alphas_b(const RaggedArgs &r, unsigned waves, hipStream_t st);
+template <int B>
+hipError_t embed_key_ragged_alphas_b(const RaggedKeyArgs &r, unsigned waves, hipStream_t st);
+template <int B>
+hipError_t extract_ragged_alphas_b(const RaggedArgs &r, unsigned waves, hipStream_t st);
+template <int B>
+hipError_t extract_keyed_ragged_alphas_b(const RaggedArgs &r, unsigned waves, hipStream_t st, int px);
+template <int B>
+hipError_t embed_ragged_alphas_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
+template <int B>
+hipError_t embed_key_ragged_alphas_fixup_b(const RaggedKeyArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
+                                           hipStream_t st);
+template <int B>
+hipError_t extract_ragged_alphas_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries, hipStream_t st);
+template <int B>
+hipError_t extract_keyed_ragged_alphas_fixup_b(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
+                                               hipStream_t st, int px);
+template <int B>
+hipError_t embed_rank1_ragged_alphas_b(const RaggedRank1Args &r, unsigned waves, hipStream_t st);
+template <int B>
+hipError_t embed_ragged_alphas_list_b(const RaggedRank1Args &r, unsigned shards, hipStream_t st);
+
 #if defined(__HIPCC__)
 // The table through the constant address space: a load from it at a wave-uniform address is a
 // scalar load, so what a strip wave reads of its frame stays in SGPRs (the VGPR budget of
@@ -175,6 +228,20 @@ __device__ __forceinline__ RaggedKeyK *ragged_key_const(float *const *p) { retur
 // and the shard side table (RaggedRank1Args::shards)
 using RaggedShardsK = const TMF_CONST_AS RaggedShards;
 __device__ __forceinline__ RaggedShardsK *ragged_shards_const(const RaggedShards *p) { return (RaggedShardsK *)p; }
+// and the alpha side table (RaggedArgs::alphas_off)
+using RaggedAlphaK = const TMF_CONST_AS RaggedAlpha;
+
+// Frame f's entry of the alpha table, in f's address space: a strip, pre-pass or list wave holds
+// its frame in the constant address space (wave-uniform: a scalar load), a fixup lane the frame of
+// its listed block in the generic one (a wave holds blocks of several frames).
+__device__ __forceinline__ RaggedAlphaK *ragged_alpha_entry(const RaggedArgs &r, RaggedFrameK *f)
+{
+    return (RaggedAlphaK *)((const TMF_CONST_AS uint8_t *)ragged_const(r.frames) + r.alphas_off) + (f - ragged_const(r.frames));
+}
+__device__ __forceinline__ const RaggedAlpha *ragged_alpha_entry(const RaggedArgs &r, const RaggedFrame *f)
+{
+    return (const RaggedAlpha *)((const uint8_t *)r.frames + r.alphas_off) + (f - r.frames);
+}
 
 // the frame that owns flat index x: the last i in [0, n) with prefix(i) <= x (frames with
 // nothing to do share their successor's prefix and are never found)
@@ -190,8 +257,12 @@ __device__ __forceinline__ int ragged_find(int n, uint64_t x, Prefix prefix)
     return lo;
 }
 
-// the one-frame views of frame f (a table entry in either address space)
-template <class F>
+// the one-frame views of frame f (a table entry in either address space); PF: the per-frame form,
+// the frame's alpha from the alpha table.  The form is a template argument of every view and of
+// every helper between a kernel and its view -- a unit's kernels pass kRaggedAlphas -- so the two
+// forms of a helper are two functions by name, never one name with two bodies.
+constexpr bool kRaggedAlphas = TMF_RAGGED_ALPHAS != 0;
+template <bool PF, class F>
 __device__ __forceinline__ EmbedArgs ragged_embed_view(const RaggedArgs &r, F *f)
 {
     EmbedArgs a;
@@ -208,7 +279,8 @@ __device__ __forceinline__ EmbedArgs ragged_embed_view(const RaggedArgs &r, F *f
     a.nbw = f->nbw;
     a.strips_per_row = f->strips_per_row;
     a.aligned = f->aligned;
-    a.alpha = r.alpha;
+    if constexpr (PF) a.alpha = ragged_alpha_entry(r, f)->alpha;
+    else a.alpha = r.alpha;
     a.fb_list = r.fb_list;
     a.fb_count = r.fb_count;
     a.fb_bad = r.fb_bad;
@@ -220,7 +292,7 @@ __device__ __forceinline__ EmbedArgs ragged_embed_view(const RaggedArgs &r, F *f
     return a;
 }
 
-template <class F>
+template <bool PF, class F>
 __device__ __forceinline__ ExtractArgs ragged_extract_view(const RaggedArgs &r, F *f)
 {
     ExtractArgs a;
@@ -237,7 +309,8 @@ __device__ __forceinline__ ExtractArgs ragged_extract_view(const RaggedArgs &r, 
     a.nbw = f->nbw;
     a.strips_per_row = f->strips_per_row;
     a.aligned = f->aligned;
-    a.alpha32 = r.alpha32;
+    if constexpr (PF) a.alpha32 = ragged_alpha_entry(r, f)->alpha32;
+    else a.alpha32 = r.alpha32;
     a.fb_list = r.fb_list;
     a.fb_count = r.fb_count;
     a.fb_bad = r.fb_bad;
@@ -248,7 +321,7 @@ __device__ __forceinline__ ExtractArgs ragged_extract_view(const RaggedArgs &r, 
 }
 
 // keyed extraction: one image per frame; in1 is the key (keyed extract), out the key output (map) or the tile
-template <class F>
+template <bool PF, class F>
 __device__ __forceinline__ KeyedArgs ragged_keyed_view(const RaggedArgs &r, F *f)
 {
     KeyedArgs a;
@@ -267,7 +340,8 @@ __device__ __forceinline__ KeyedArgs ragged_keyed_view(const RaggedArgs &r, F *f
     a.nbw = f->nbw;
     a.strips_per_row = f->strips_per_row;
     a.aligned = f->aligned;
-    a.alpha32 = r.alpha32;
+    if constexpr (PF) a.alpha32 = ragged_alpha_entry(r, f)->alpha32;
+    else a.alpha32 = r.alpha32;
     a.fb_list = r.fb_list;
     a.fb_count = r.fb_count;
     a.fb_bad = r.fb_bad;

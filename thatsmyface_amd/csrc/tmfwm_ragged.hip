@@ -10,40 +10,47 @@ int ragged_strip_blocks(int block)
     return block_value(block, 1, [](auto b) { return (int)Geo<b()>::BPW; });  // (the callers have checked the size)
 }
 
+// (r.alphas_off set: the per-frame form, the *_alphas launchers of the units built with -DTMF_RAGGED_ALPHAS=1)
+//
 // a launch is one workgroup per strip wave: the caller's chunks keep it inside the grid limit
 constexpr int64_t kGridMax = 0x7FFFFFFF;
 
 hipError_t launch_embed_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st)
 {
     if (waves <= 0 || waves > kGridMax) return hipErrorInvalidValue;
-    return for_block(r.block, [&](auto b) { return embed_ragged_b<b()>(r, (unsigned)waves, st); });
+    return for_block(r.block, [&](auto b) { return r.alphas_off ? embed_ragged_alphas_b<b()>(r, (unsigned)waves, st) : embed_ragged_b<b()>(r, (unsigned)waves, st); });
 }
 
 hipError_t launch_embed_rank1_ragged(const RaggedRank1Args &r, int64_t waves, uint32_t shards, hipStream_t st)
 {
     if (waves <= 0 || waves > kGridMax || shards > kListShards || (r.slow_list && shards == 0)) return hipErrorInvalidValue;
     return for_block(r.block, [&](auto b) {
-        const hipError_t e = embed_rank1_ragged_b<b()>(r, (unsigned)waves, st);
-        return e != hipSuccess || !r.slow_list ? e : embed_ragged_list_b<b()>(r, shards, st);
+        const bool pf = r.alphas_off != 0;
+        const hipError_t e = pf ? embed_rank1_ragged_alphas_b<b()>(r, (unsigned)waves, st) : embed_rank1_ragged_b<b()>(r, (unsigned)waves, st);
+        if (e != hipSuccess || !r.slow_list) return e;
+        return pf ? embed_ragged_alphas_list_b<b()>(r, shards, st) : embed_ragged_list_b<b()>(r, shards, st);
     });
 }
 
 hipError_t launch_embed_key_ragged(const RaggedKeyArgs &r, int64_t waves, hipStream_t st)
 {
     if (waves <= 0 || waves > kGridMax) return hipErrorInvalidValue;
-    return for_block(r.block, [&](auto b) { return embed_key_ragged_b<b()>(r, (unsigned)waves, st); });
+    return for_block(r.block, [&](auto b) { return r.alphas_off ? embed_key_ragged_alphas_b<b()>(r, (unsigned)waves, st) : embed_key_ragged_b<b()>(r, (unsigned)waves, st); });
 }
 
 hipError_t launch_embed_key_ragged_fixup(const RaggedKeyArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
                                          hipStream_t st)
 {
-    return for_block(r.block, [&](auto b) { return embed_key_ragged_fixup_b<b()>(r, list, count, max_entries, st); });
+    return for_block(r.block, [&](auto b) {
+        return r.alphas_off ? embed_key_ragged_alphas_fixup_b<b()>(r, list, count, max_entries, st)
+                            : embed_key_ragged_fixup_b<b()>(r, list, count, max_entries, st);
+    });
 }
 
 hipError_t launch_extract_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st)
 {
     if (waves <= 0 || waves > kGridMax) return hipErrorInvalidValue;
-    return for_block(r.block, [&](auto b) { return extract_ragged_b<b()>(r, (unsigned)waves, st); });
+    return for_block(r.block, [&](auto b) { return r.alphas_off ? extract_ragged_alphas_b<b()>(r, (unsigned)waves, st) : extract_ragged_b<b()>(r, (unsigned)waves, st); });
 }
 
 hipError_t launch_sigma1_map_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st, int px)
@@ -55,19 +62,26 @@ hipError_t launch_sigma1_map_ragged(const RaggedArgs &r, int64_t waves, hipStrea
 hipError_t launch_extract_keyed_ragged(const RaggedArgs &r, int64_t waves, hipStream_t st, int px)
 {
     if (waves <= 0 || waves > kGridMax || (px != 3 && px != 4)) return hipErrorInvalidValue;
-    return for_block(r.block, [&](auto b) { return extract_keyed_ragged_b<b()>(r, (unsigned)waves, st, px); });
+    return for_block(r.block, [&](auto b) {
+        return r.alphas_off ? extract_keyed_ragged_alphas_b<b()>(r, (unsigned)waves, st, px) : extract_keyed_ragged_b<b()>(r, (unsigned)waves, st, px);
+    });
 }
 
 hipError_t launch_embed_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
                                      hipStream_t st)
 {
-    return for_block(r.block, [&](auto b) { return embed_ragged_fixup_b<b()>(r, list, count, max_entries, st); });
+    return for_block(r.block, [&](auto b) {
+        return r.alphas_off ? embed_ragged_alphas_fixup_b<b()>(r, list, count, max_entries, st) : embed_ragged_fixup_b<b()>(r, list, count, max_entries, st);
+    });
 }
 
 hipError_t launch_extract_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
                                        hipStream_t st)
 {
-    return for_block(r.block, [&](auto b) { return extract_ragged_fixup_b<b()>(r, list, count, max_entries, st); });
+    return for_block(r.block, [&](auto b) {
+        return r.alphas_off ? extract_ragged_alphas_fixup_b<b()>(r, list, count, max_entries, st)
+                            : extract_ragged_fixup_b<b()>(r, list, count, max_entries, st);
+    });
 }
 
 hipError_t launch_sigma1_ragged_fixup(const RaggedArgs &r, const uint32_t *list, const uint32_t *count, int64_t max_entries,
@@ -81,7 +95,10 @@ hipError_t launch_extract_keyed_ragged_fixup(const RaggedArgs &r, const uint32_t
                                              hipStream_t st, int px)
 {
     if (px != 3 && px != 4) return hipErrorInvalidValue;
-    return for_block(r.block, [&](auto b) { return extract_keyed_ragged_fixup_b<b()>(r, list, count, max_entries, st, px); });
+    return for_block(r.block, [&](auto b) {
+        return r.alphas_off ? extract_keyed_ragged_alphas_fixup_b<b()>(r, list, count, max_entries, st, px)
+                            : extract_keyed_ragged_fixup_b<b()>(r, list, count, max_entries, st, px);
+    });
 }
 
 // The edge pixels of every frame of the chunk on one flat index over the table's edge prefix;

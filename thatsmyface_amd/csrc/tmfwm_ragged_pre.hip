@@ -4,6 +4,9 @@
 // tmfwm_rank1.hip: the default scheduler) and the list pass of TMFWM_ROUTE_RANK1
 // (embed_kernel<b, true>: at b = 8 under max-ILP, tmfwm_embed8.hip); so at b = 8 the Makefile
 // makes two objects of this file, TMF_RAGGED_PRE_PART = 1 and 2 (unset: both).
+//
+// With -DTMF_RAGGED_ALPHAS=1 the unit holds the per-frame form of both kernels instead
+// (tmfwm_ragged.h): the wave's frame's alpha from the alpha table, one more scalar load.
 #include "tmfwm_rank1.h"
 #include "tmfwm_ragged_strips.h"
 
@@ -22,7 +25,7 @@ namespace tmf {
 // (TMFWM_ROUTE_RANK1) or to the dgesdd-route list (TMFWM_ROUTE_RANK1_REFERENCE), by its
 // chunk-relative id either way.
 template <int B>
-__global__ __launch_bounds__(64, kRank1Waves<B>) void embed_rank1_ragged_kernel(RaggedRank1Args rag)
+__global__ __launch_bounds__(64, kRank1Waves<B>) void TMF_RAGGED_NAME(embed_rank1_ragged, _kernel)(RaggedRank1Args rag)
 {
     constexpr int L = Geo<B>::L, R = Geo<B>::R, LD = B + 1, NW = Geo<B>::NW;
     constexpr double u53 = 1.1102230246251565e-16;  // 2^-53
@@ -32,7 +35,7 @@ __global__ __launch_bounds__(64, kRank1Waves<B>) void embed_rank1_ragged_kernel(
     const int lane = threadIdx.x & 63, g = lane / L, q = lane % L;
     float *tile = lds + g * B * LD;
     RaggedFrameK *f = ragged_wave_frame(rag);
-    const EmbedArgs a = ragged_embed_view(rag, f);
+    const EmbedArgs a = ragged_embed_view<kRaggedAlphas>(rag, f);
     uint32_t id;
     const StripPos pos = ragged_strip_pos<B>(f, id);
 #define TMF_RANK1_LEFT                                                                                         \
@@ -49,13 +52,13 @@ __global__ __launch_bounds__(64, kRank1Waves<B>) void embed_rank1_ragged_kernel(
 }
 
 template <int B>
-hipError_t embed_rank1_ragged_b(const RaggedRank1Args &r, unsigned waves, hipStream_t st)
+hipError_t TMF_RAGGED_NAME(embed_rank1_ragged, _b)(const RaggedRank1Args &r, unsigned waves, hipStream_t st)
 {
-    hipLaunchKernelGGL((embed_rank1_ragged_kernel<B>), dim3(waves), dim3(64), 0, st, r);
+    hipLaunchKernelGGL((TMF_RAGGED_NAME(embed_rank1_ragged, _kernel)<B>), dim3(waves), dim3(64), 0, st, r);
     return hipGetLastError();
 }
 
-template hipError_t embed_rank1_ragged_b<TMF_B>(const RaggedRank1Args &, unsigned, hipStream_t);
+template hipError_t TMF_RAGGED_NAME(embed_rank1_ragged, _b)<TMF_B>(const RaggedRank1Args &, unsigned, hipStream_t);
 #endif
 
 #if TMF_RAGGED_PRE_PART & 2
@@ -64,7 +67,7 @@ template hipError_t embed_rank1_ragged_b<TMF_B>(const RaggedRank1Args &, unsigne
 // the wave's listed blocks are one frame's and embed_blocks<B, true> runs on that frame's view;
 // what it does not certify goes on to fb_list.
 template <int B>
-__global__ __launch_bounds__(64, kEmbedWaves<B>) void embed_ragged_list_kernel(RaggedRank1Args r)
+__global__ __launch_bounds__(64, kEmbedWaves<B>) void TMF_RAGGED_NAME(embed_ragged, _list_kernel)(RaggedRank1Args r)
 {
     constexpr int L = Geo<B>::L, BPW = Geo<B>::BPW, TS = kEmbedTS<B>;
     __shared__ __attribute__((aligned(16))) float lds_all[BPW * TS + kHiPad<B> + kLds2Floats<B>];  // as embed_kernel
@@ -73,7 +76,7 @@ __global__ __launch_bounds__(64, kEmbedWaves<B>) void embed_ragged_list_kernel(R
     RaggedShardsK *tab = ragged_shards_const(r.shards);
     const int fi = ragged_find(r.nframes, s, [&](int i) { return tab[i].sh0; });
     RaggedFrameK *f = ragged_const(r.frames) + fi;
-    const EmbedArgs a = ragged_embed_view(r, f);
+    const EmbedArgs a = ragged_embed_view<kRaggedAlphas>(r, f);
     const uint32_t block0 = f->block0, nbw = (uint32_t)f->nbw;
     const uint32_t n = r.slow_shards[s * kShardStride];
     const uint32_t base = ragged_seg_base(block0, (uint32_t)f->nbh, nbw, tab[fi].n, s - tab[fi].sh0);
@@ -93,13 +96,13 @@ __global__ __launch_bounds__(64, kEmbedWaves<B>) void embed_ragged_list_kernel(R
 }
 
 template <int B>
-hipError_t embed_ragged_list_b(const RaggedRank1Args &r, unsigned shards, hipStream_t st)
+hipError_t TMF_RAGGED_NAME(embed_ragged, _list_b)(const RaggedRank1Args &r, unsigned shards, hipStream_t st)
 {
-    hipLaunchKernelGGL((embed_ragged_list_kernel<B>), dim3(shards), dim3(64), 0, st, r);
+    hipLaunchKernelGGL((TMF_RAGGED_NAME(embed_ragged, _list_kernel)<B>), dim3(shards), dim3(64), 0, st, r);
     return hipGetLastError();
 }
 
-template hipError_t embed_ragged_list_b<TMF_B>(const RaggedRank1Args &, unsigned, hipStream_t);
+template hipError_t TMF_RAGGED_NAME(embed_ragged, _list_b)<TMF_B>(const RaggedRank1Args &, unsigned, hipStream_t);
 #endif
 
 }  // namespace tmf

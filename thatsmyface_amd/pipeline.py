@@ -20,6 +20,10 @@ Results come back in input order and are byte-identical to
 ``img.save(format="PNG")`` per image.  The device stage is a parameter so the
 pipeline logic is testable on CPU (tests/test_pipeline.py).
 
+``custom_settings`` may be a sequence of dicts, one per image (uploads of several sessions, each
+with its own sliders): a group is then split by ``(block_size, svd_route)`` and each part is one
+ragged call with its images' alphas (``embed_ragged(alpha=[...])``).
+
 ``extract_images`` is the extraction counterpart for a verifier that stores keys instead of
 originals: decode on the worker threads, then per group of ``batch_images`` images of any
 sizes one upload, one ``extract_keyed_ragged`` and one copy back (``KeyedExtractStage``).
@@ -73,7 +77,8 @@ class GpuStage:
     may be a list or tuple of watermarks, one per image: the stage is then called as
     ``stage(rgb, i)`` and keeps its per-size tile cache per watermark.  With ``return_keys`` the
     embed is ``embed_with_key`` and the stage returns (pixels, wait, key), the key copied back
-    with the pixels."""
+    with the pixels.  With per-image settings the stage of a block size and route is called with
+    ``settings=`` the image's resolved settings and takes its alpha from there."""
 
     def __init__(self, watermark_data, block: int, alpha: float, preserve_ratio: bool, device=None, route: str = SVD_ROUTE,
                  return_keys: bool = False):
@@ -102,8 +107,9 @@ class GpuStage:
                 self.tiles[key] = self.batch.prepare_tile(self.wm_grey[index], nbh, nbw, self.preserve_ratio, stream=self.stream)
         return self.tiles[key]
 
-    def __call__(self, rgb: np.ndarray, index: int = 0):
+    def __call__(self, rgb: np.ndarray, index: int = 0, settings: dict | None = None):
         torch = self.torch
+        alpha = self.alpha if settings is None else float(settings["alpha"])
         h, w = rgb.shape[:2]
         nbh, nbw = h // self.block, w // self.block
         if nbh == 0 or nbw == 0:
@@ -117,10 +123,10 @@ class GpuStage:
             dev_in = host_in.to(self.device, non_blocking=True)
             dev_key = None
             if self.return_keys:
-                dev_out, dev_key = self.batch.embed_with_key(dev_in, tile, self.block, self.alpha, stream=self.stream, route=self.route)
+                dev_out, dev_key = self.batch.embed_with_key(dev_in, tile, self.block, alpha, stream=self.stream, route=self.route)
                 host_key.copy_(dev_key, non_blocking=True)
             else:
-                dev_out = self.batch.embed_batch(dev_in, tile, self.block, self.alpha, stream=self.stream, route=self.route)
+                dev_out = self.batch.embed_batch(dev_in, tile, self.block, alpha, stream=self.stream, route=self.route)
             host_out.copy_(dev_out, non_blocking=True)
             done = torch.cuda.Event()
             done.record(self.stream)
@@ -144,7 +150,9 @@ class RaggedGpuStage(GpuStage):
     Called as ``stage(rgbs, indices)`` with the group's pixel arrays and their positions in the
     input (the watermark of image ``i`` is watermark ``i`` when there is one per image); returns
     one ``(pixels, wait)`` per image, in the group's order -- with ``return_keys``, by one
-    ``embed_with_key_ragged``, one ``(pixels, wait, key)`` per image."""
+    ``embed_with_key_ragged``, one ``(pixels, wait, key)`` per image.  With per-image settings
+    ``settings=`` is the group's resolved settings, one dict per image, and the one ragged call
+    takes their alphas."""
 
     def _group_tiles(self, keys):
         """The tiles of a group's (watermark, nbh, nbw) keys: those the cache does not hold, each
@@ -160,8 +168,9 @@ class RaggedGpuStage(GpuStage):
                 self.tiles.update(made)
         return [made[k] if k in made else self.tiles[k] for k in keys]
 
-    def __call__(self, rgbs, indices):
+    def __call__(self, rgbs, indices, settings=None):
         torch = self.torch
+        alpha = self.alpha if settings is None else [float(s["alpha"]) for s in settings]
         keys, host_in, host_out, host_key = [], [], [], []
         for rgb, index in zip(rgbs, indices):
             h, w = rgb.shape[:2]
@@ -183,10 +192,10 @@ class RaggedGpuStage(GpuStage):
             rank1 = self.route in ("rank1", "rank1_reference")
             if self.return_keys:
                 embed = self.batch.embed_with_key_ragged_rank1 if rank1 else self.batch.embed_with_key_ragged
-                dev_out, dev_key = embed(dev_in, tiles, self.block, self.alpha, stream=self.stream, route=self.route)
+                dev_out, dev_key = embed(dev_in, tiles, self.block, alpha, stream=self.stream, route=self.route)
             else:
                 embed = self.batch.embed_ragged_rank1 if rank1 else self.batch.embed_ragged
-                dev_out = embed(dev_in, tiles, self.block, self.alpha, stream=self.stream, route=self.route)
+                dev_out = embed(dev_in, tiles, self.block, alpha, stream=self.stream, route=self.route)
             for ho, do in zip(host_out + host_key, list(dev_out) + list(dev_key)):
                 ho.copy_(do, non_blocking=True)
             done = torch.cuda.Event()
@@ -217,7 +226,9 @@ class KeyedExtractStage:
 
     Called as ``stage(rgbs, keys, indices)``; returns one ``(tile, wait)`` per image, in the
     group's order, where ``wait()`` blocks until the copy back has landed.  An image smaller
-    than a block has no block: its tile is empty and it takes no part in the device call."""
+    than a block has no block: its tile is empty and it takes no part in the device call.  With
+    per-image settings ``settings=`` is the group's resolved settings and the call takes their
+    alphas."""
 
     def __init__(self, block: int, alpha: float, device=None, route: str = SVD_ROUTE):
         import torch
@@ -229,7 +240,7 @@ class KeyedExtractStage:
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.stream = torch.cuda.Stream(device=self.device)
 
-    def __call__(self, rgbs, keys, indices):
+    def __call__(self, rgbs, keys, indices, settings=None):
         torch, b = self.torch, self.block
         live = [j for j, rgb in enumerate(rgbs) if rgb.shape[0] >= b and rgb.shape[1] >= b]
         tiles = [np.zeros((rgb.shape[0] // b, rgb.shape[1] // b), np.uint8) for rgb in rgbs]
@@ -266,7 +277,8 @@ class KeyedExtractStage:
                 outs.append(dev_out[o:o + nbh * nbw].view(nbh, nbw))
             # on a rank-1 route the keyed extract is the hybrid enclosure, as every single-size keyed call has it
             route = "hybrid" if self.route in ("rank1", "rank1_reference") else self.route
-            self.batch.extract_keyed_ragged(frames, dkeys, b, self.alpha, out=outs, stream=self.stream, route=route)
+            alpha = self.alpha if settings is None else [float(settings[j]["alpha"]) for j in live]
+            self.batch.extract_keyed_ragged(frames, dkeys, b, alpha, out=outs, stream=self.stream, route=route)
             host_out.copy_(dev_out, non_blocking=True)
             done = torch.cuda.Event()
             done.record(self.stream)
@@ -279,6 +291,40 @@ class KeyedExtractStage:
         for j, o in zip(live, out_at):
             tiles[j] = res[o:o + tiles[j].size].reshape(tiles[j].shape)
         return [(t, wait if j in live else None) for j, t in enumerate(tiles)]
+
+
+def _resolved(settings) -> dict:
+    """One image's settings with the defaults filled in, as the drop-ins read them."""
+    s = settings or {}
+    return {"block_size": int(s.get("block_size", BLOCK_SIZE)), "alpha": float(s.get("alpha", ALPHA)),
+            "svd_route": s.get("svd_route") or os.environ.get("TMFWM_SVD_ROUTE") or SVD_ROUTE}  # as watermarking._route
+
+
+def _per_image_settings(custom_settings, n: int) -> list:
+    if len(custom_settings) != n:
+        raise ValueError(f"{len(custom_settings)} settings for {n} images: custom_settings is one dict, or one per image")
+    return [_resolved(s) for s in custom_settings]
+
+
+def _parts(indices, resolved) -> dict:
+    """A group's positions by (block_size, svd_route), in order of first appearance: one ragged
+    call takes one block size and one route, and any alphas."""
+    parts: dict = {}
+    for j, i in enumerate(indices):
+        parts.setdefault((resolved[i]["block_size"], resolved[i]["svd_route"]), []).append(j)
+    return parts
+
+
+def _staged_parts(indices, resolved, call) -> list:
+    """The group's results in its own order, from one call(block, route, positions, settings) per part."""
+    results = [None] * len(indices)
+    for (block, route), js in _parts(indices, resolved).items():
+        part = call(block, route, js, [resolved[indices[j]] for j in js])
+        if len(part) != len(js):
+            raise ValueError(f"the device stage returned {len(part)} results for {len(js)} images")
+        for j, r in zip(js, part):
+            results[j] = r
+    return results
 
 
 def extract_images(images: Iterable, keys: Sequence, custom_settings: dict | None = None, batch_images: int = 16,
@@ -294,8 +340,15 @@ def extract_images(images: Iterable, keys: Sequence, custom_settings: dict | Non
     (``KeyedExtractStage``; a custom ``device_stage`` is called as ``stage(rgbs, keys, indices)``
     and returns one ``(tile, wait)`` per image).  A key that is not float32 (TypeError) or whose
     shape does not fit its image (ValueError) raises before any device work for its group.
-    Decoding the tiles' QR content stays with the caller (``qrcode_generator.qrcode_to_text``)."""
-    settings = custom_settings or {}
+    Decoding the tiles' QR content stays with the caller (``qrcode_generator.qrcode_to_text``).
+
+    ``custom_settings`` may be a list or tuple of dicts, one per image (another length is a
+    ValueError): result i is then ``extract_watermark_keyed(images[i], keys[i], custom_settings[i])``.
+    Each group is split by ``(block_size, svd_route)`` and each part is one ``extract_keyed_ragged``
+    with its images' alphas; a custom ``device_stage`` is called once per part as
+    ``stage(rgbs, keys, indices, settings=[...])`` with the part's resolved settings."""
+    per_settings = isinstance(custom_settings, (list, tuple))
+    settings = {} if per_settings else custom_settings or {}
     block = int(settings.get("block_size", BLOCK_SIZE))
     alpha = float(settings.get("alpha", ALPHA))
     route = settings.get("svd_route") or os.environ.get("TMFWM_SVD_ROUTE") or SVD_ROUTE  # as watermarking._route
@@ -303,11 +356,27 @@ def extract_images(images: Iterable, keys: Sequence, custom_settings: dict | Non
     keys = list(keys)
     if len(keys) != len(sources):
         raise ValueError(f"{len(keys)} keys for {len(sources)} images")
+    resolved = _per_image_settings(custom_settings, len(sources)) if per_settings else None
     if batch_images is None or int(batch_images) < 1:
         raise ValueError(f"batch_images must be >= 1, got {batch_images!r}")
-    if block <= 0:
-        raise ValueError(f"block_size must be positive, got {block}")
-    stage = device_stage or KeyedExtractStage(block, alpha, route=route)
+    if per_settings:
+        for r in resolved:
+            if r["block_size"] <= 0:
+                raise ValueError(f"block_size must be positive, got {r['block_size']}")
+        stages: dict = {}  # one default stage per (block size, route)
+
+        def stage(rgbs, group_keys, indices):
+            def call(b, rt, js, part_settings):
+                if device_stage is None and (b, rt) not in stages:
+                    stages[(b, rt)] = KeyedExtractStage(b, ALPHA, route=rt)
+                return (device_stage or stages[(b, rt)])([rgbs[j] for j in js], [group_keys[j] for j in js], [indices[j] for j in js],
+                                                         settings=part_settings)
+
+            return _staged_parts(indices, resolved, call)
+    else:
+        if block <= 0:
+            raise ValueError(f"block_size must be positive, got {block}")
+        stage = device_stage or KeyedExtractStage(block, alpha, route=route)
     n_workers = workers or min(16, max(2, (len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 4)))
 
     def finish(results):
@@ -324,7 +393,7 @@ def extract_images(images: Iterable, keys: Sequence, custom_settings: dict | Non
                 indices = list(range(i0, min(i0 + int(batch_images), len(decoded))))
                 rgbs = [decoded[i].result() for i in indices]
                 for i, rgb in zip(indices, rgbs):
-                    _check_key(i, keys[i], rgb.shape[0], rgb.shape[1], block)
+                    _check_key(i, keys[i], rgb.shape[0], rgb.shape[1], resolved[i]["block_size"] if per_settings else block)
                 results = stage(rgbs, [keys[i] for i in indices], indices)
                 if len(results) != len(indices):
                     raise ValueError(f"the device stage returned {len(results)} results for {len(indices)} images")
@@ -359,7 +428,18 @@ def embed_images(images: Iterable, watermark_data, preserve_ratio: bool = True, 
     ``key``, bit for bit ``watermarking.extraction_key(image, custom_settings)`` of the original
     image, out of the same device call as the pixels (``embed_with_key`` /
     ``embed_with_key_ragged``) -- what ``extract_images`` takes with the watermarked images.  A
-    custom ``device_stage`` then returns ``(pixels, wait, key)`` per image."""
+    custom ``device_stage`` then returns ``(pixels, wait, key)`` per image.
+
+    ``custom_settings`` may be a list or tuple of dicts, one per image (another length is a
+    ValueError): result i is then ``embed_watermark(images[i], watermark_i, preserve_ratio,
+    custom_settings[i])``.  With ``batch_images=K`` each group of K images is split by
+    ``(block_size, svd_route)`` and each part goes through one ragged call with its images'
+    alphas; without it the per-image stage takes each image's settings.  A custom ``device_stage``
+    additionally receives ``settings=``: the part's resolved settings, one dict per image (the
+    image's dict on the per-image path).  A single dict behaves as it always has."""
+    if isinstance(custom_settings, (list, tuple)):
+        return _embed_images_per_settings(images, watermark_data, preserve_ratio, custom_settings, workers, device_stage,
+                                          batch_images, return_keys)
     settings = custom_settings or {}
     block = int(settings.get("block_size", BLOCK_SIZE))
     alpha = float(settings.get("alpha", ALPHA))
@@ -394,4 +474,53 @@ def embed_images(images: Iterable, watermark_data, preserve_ratio: bool = True, 
             return [f.result() for f in encoded]
         for i, fut in enumerate(decoded):  # the device stage runs in order on this thread
             encoded.append(pool.submit(_encode, *checked(stage(fut.result(), i) if per_image else stage(fut.result()))))
+        return [f.result() for f in encoded]
+
+
+def _embed_images_per_settings(images, watermark_data, preserve_ratio, custom_settings, workers, device_stage, batch_images,
+                               return_keys) -> list[Embedded]:
+    """embed_images with one settings dict per image."""
+    sources: Sequence = list(images)
+    per_image = isinstance(watermark_data, (list, tuple))
+    if per_image and len(watermark_data) != len(sources):
+        raise ValueError(f"{len(watermark_data)} watermarks for {len(sources)} images")
+    resolved = _per_image_settings(custom_settings, len(sources))
+    if batch_images is not None and int(batch_images) < 1:
+        raise ValueError(f"batch_images must be >= 1 or None, got {batch_images!r}")
+    stages: dict = {}  # one default stage per (block size, route)
+
+    def stage_of(block, route):
+        if device_stage is not None:
+            return device_stage
+        if (block, route) not in stages:
+            stages[(block, route)] = (GpuStage if batch_images is None else RaggedGpuStage)(
+                watermark_data, block, ALPHA, preserve_ratio, route=route, **({"return_keys": True} if return_keys else {}))
+        return stages[(block, route)]
+
+    arity = 3 if return_keys else 2
+
+    def checked(result):
+        if len(result) != arity:
+            raise ValueError(f"the device stage returned {len(result)} values per image, {arity} expected"
+                             + (" (pixels, wait, key)" if return_keys else ""))
+        return result
+
+    n_workers = workers or min(16, max(2, (len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 4)))
+    with ThreadPoolExecutor(n_workers, thread_name_prefix="tmf-io") as pool:
+        decoded: list[Future] = [pool.submit(_decode, s) for s in sources]
+        encoded: list[Future] = []
+        if batch_images is not None:
+            for i0 in range(0, len(decoded), int(batch_images)):
+                indices = list(range(i0, min(i0 + int(batch_images), len(decoded))))
+                rgbs = [decoded[i].result() for i in indices]
+
+                def call(block, route, js, part_settings):
+                    return stage_of(block, route)([rgbs[j] for j in js], [indices[j] for j in js], settings=part_settings)
+
+                encoded.extend(pool.submit(_encode, *checked(r)) for r in _staged_parts(indices, resolved, call))
+            return [f.result() for f in encoded]
+        for i, fut in enumerate(decoded):
+            stage = stage_of(resolved[i]["block_size"], resolved[i]["svd_route"])
+            res = stage(fut.result(), i, settings=resolved[i]) if per_image else stage(fut.result(), settings=resolved[i])
+            encoded.append(pool.submit(_encode, *checked(res)))
         return [f.result() for f in encoded]

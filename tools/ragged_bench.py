@@ -25,12 +25,19 @@ embed_ragged_rank1 on "rank1" against embed_ragged on "hybrid" (base), on "rank1
 embed_ragged on "reference" (base), and each of the two against the loop of 64 single-frame
 embed_batch calls on the same rank-1 route (base).
 
+Workload S (one alpha per frame): workload A's frames and tiles with 64 distinct
+alphas in [0.02, 0.5].  embed_ragged(alpha=list) against the loop of 64 single-frame embed_batch
+calls at those alphas (base); extract_keyed_ragged(alpha=list) against its loop (base); and each of
+the two against the same call with one alpha (base): what the per-frame form costs.  With
+--parent-lib PATH (a libtmfwm.so built from the parent commit, loaded into the same process) also
+the uniform embed_ragged and extract_keyed_ragged of this build against the parent's (base).
+
 Both arms of a comparison run alternately in one process, each timing a window of `inner` calls
 that ends in a device synchronise.  Every ratio comes with the A/A spread of its own run: the
 medians of the even and of the odd rounds of the same arm, as a ratio.  The arms' outputs are
 compared byte for byte before anything is timed.
 
-usage: python tools/ragged_bench.py [--workload a|b|k|e|r|ab|abk] [--rounds R] [--frames-b N]
+usage: python tools/ragged_bench.py [--workload a|b|k|e|r|s|ab|abk] [--rounds R] [--frames-b N] [--parent-lib PATH]
 """
 import argparse
 import json
@@ -44,7 +51,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from thatsmyface_amd import batch  # noqa: E402
+from thatsmyface_amd import _lib, batch  # noqa: E402
 
 SIZES = [(480, 640), (600, 800), (768, 1024), (720, 1280), (1080, 1920)]  # (H, W)
 
@@ -230,6 +237,76 @@ def workload_r(rounds, dev):
     return out
 
 
+def other_build(path):
+    """fn -> fn run on another build of the library (same ABI) in this process (_lib.open_build /
+    _lib.using), so both builds are timed in alternating windows of one run."""
+    other = _lib.open_build(path)
+
+    def on_other(fn):
+        def run():
+            with _lib.using(other):
+                return fn()
+
+        return run
+
+    return on_other
+
+
+def workload_s(rounds, dev, parent_lib):
+    b, n = 8, 64
+    picks, frames, tiles = frames_a(dev, b, n)
+    alphas = [float(a) for a in np.linspace(0.02, 0.5, n)]
+    assert len(set(alphas)) == n
+    frames1 = [f[None] for f in frames]
+    wm = batch.embed_ragged(frames, tiles, b, alphas)
+    wm1 = [w[None] for w in wm]
+    keys = batch.sigma1_map_ragged(frames, b)
+    state = {}
+    arms = {
+        "embed_loop": lambda: state.__setitem__("embed_loop", [batch.embed_batch(f, t, b, a) for f, t, a in zip(frames1, tiles, alphas)]),
+        "embed_alphas": lambda: state.__setitem__("embed_alphas", batch.embed_ragged(frames, tiles, b, alphas)),
+        "embed_uniform": lambda: state.__setitem__("embed_uniform", batch.embed_ragged(frames, tiles, b, 0.1)),
+        "embed_alphas_same": lambda: state.__setitem__("embed_alphas_same", batch.embed_ragged(frames, tiles, b, [0.1] * n)),
+        "keyed_loop": lambda: state.__setitem__("keyed_loop", [batch.extract_keyed(w, k, b, a) for w, k, a in zip(wm1, keys, alphas)]),
+        "keyed_alphas": lambda: state.__setitem__("keyed_alphas", batch.extract_keyed_ragged(wm, keys, b, alphas)),
+        "keyed_uniform": lambda: state.__setitem__("keyed_uniform", batch.extract_keyed_ragged(wm, keys, b, 0.1)),
+        "keyed_alphas_same": lambda: state.__setitem__("keyed_alphas_same", batch.extract_keyed_ragged(wm, keys, b, [0.1] * n)),
+    }
+    if parent_lib:
+        on_parent = other_build(parent_lib)
+        arms["embed_parent"] = on_parent(lambda: state.__setitem__("embed_parent", batch.embed_ragged(frames, tiles, b, 0.1)))
+        arms["keyed_parent"] = on_parent(lambda: state.__setitem__("keyed_parent", batch.extract_keyed_ragged(wm, keys, b, 0.1)))
+    for fn in arms.values():
+        fn()
+    torch.cuda.synchronize()
+    for i in range(n):
+        assert torch.equal(state["embed_loop"][i][0], state["embed_alphas"][i]), ("embed differs from the loop", i)
+        assert torch.equal(state["embed_loop"][i][0], wm[i]), ("embed differs from the loop", i)
+        assert torch.equal(state["keyed_loop"][i][0], state["keyed_alphas"][i]), ("keyed extract differs from the loop", i)
+        assert torch.equal(state["embed_uniform"][i], state["embed_alphas_same"][i]), ("the per-frame form differs from the uniform one", i)
+        assert torch.equal(state["keyed_uniform"][i], state["keyed_alphas_same"][i]), ("the per-frame form differs from the uniform one", i)
+        if parent_lib:
+            assert torch.equal(state["embed_uniform"][i], state["embed_parent"][i]), ("embed differs from the parent build", i)
+            assert torch.equal(state["keyed_uniform"][i], state["keyed_parent"][i]), ("keyed extract differs from the parent build", i)
+    extra = {"block": b, "megapixels": round(sum(h * w for h, w in picks) / 1e6, 1), "alphas": [alphas[0], alphas[-1]], "outputs_equal": True}
+    out = [compare("S1", {"base": arms["embed_loop"], "ragged": arms["embed_alphas"]}, 10, rounds,
+                   {"what": "64 images, 64 alphas, embed: embed_ragged(alpha=list) vs loop of single-frame embed_batch (base)", **extra}),
+           compare("S2", {"base": arms["keyed_loop"], "ragged": arms["keyed_alphas"]}, 10, rounds,
+                   {"what": "64 images, 64 alphas, keyed extract: extract_keyed_ragged(alpha=list) vs loop of single-frame extract_keyed "
+                            "(base)", **extra}),
+           compare("S3", {"base": arms["embed_uniform"], "ragged": arms["embed_alphas"]}, 10, rounds,
+                   {"what": "64 images embed: embed_ragged(alpha=list) vs embed_ragged with one alpha (base)", **extra}),
+           compare("S4", {"base": arms["keyed_uniform"], "ragged": arms["keyed_alphas"]}, 10, rounds,
+                   {"what": "64 images keyed extract: extract_keyed_ragged(alpha=list) vs extract_keyed_ragged with one alpha (base)", **extra})]
+    if parent_lib:
+        out += [compare("S5", {"base": arms["embed_parent"], "ragged": arms["embed_uniform"]}, 10, rounds,
+                        {"what": "64 images embed, one alpha: embed_ragged of this build vs the parent commit's build (base)", **extra}),
+                compare("S6", {"base": arms["keyed_parent"], "ragged": arms["keyed_uniform"]}, 10, rounds,
+                        {"what": "64 images keyed extract, one alpha: extract_keyed_ragged of this build vs the parent commit's build (base)",
+                         **extra})]
+    return out
+
+
 def workload_b(rounds, dev, n):
     out = []
     for cover in ("noise", "photo"):
@@ -263,9 +340,10 @@ def workload_b(rounds, dev, n):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", default="ab", choices=("a", "b", "k", "e", "r", "ab", "abk"))
+    ap.add_argument("--workload", default="ab", choices=("a", "b", "k", "e", "r", "s", "ab", "abk"))
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--frames-b", type=int, default=256)
+    ap.add_argument("--parent-lib", default=None, help="workload s: a libtmfwm.so of the parent commit to time the uniform calls against")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ragged_bench: no GPU (there is no CPU fallback to time)")
@@ -281,6 +359,8 @@ def main():
         workload_e(a.rounds, dev)
     if "r" in a.workload:
         workload_r(a.rounds, dev)
+    if "s" in a.workload:
+        workload_s(a.rounds, dev, a.parent_lib)
 
 
 if __name__ == "__main__":

@@ -20,6 +20,7 @@ SIZES = (4, 6, 8, 10, 12, 14, 16)
 # compiled once per block size with -DTMF_B=<b> (the Makefile's PER_SIZE)
 PER_SIZE = ("tmfwm_fixup.hip", "tmfwm_ragged_fixup.hip", "tmfwm_keyed_fixup.hip", "tmfwm_ragged_strip.hip", "tmfwm_embed_key.hip",
             "tmfwm_ragged_pre.hip")
+ALPHAS = ("tmfwm_ragged_strip.hip", "tmfwm_ragged_fixup.hip", "tmfwm_ragged_pre.hip")
 KEYS = ["TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill",
         "LDS Size [bytes/block]"]
 
@@ -29,15 +30,19 @@ def units(csrc):
     for path in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
         tu = os.path.basename(path)
         if tu in PER_SIZE:
+            mine = []  # this source's objects
             for b in SIZES:
                 if (tu, b) == ("tmfwm_ragged_strip.hip", 8):  # two objects: embed / extract under max-ILP, the keyed kernels not
-                    out += [(tu, ["-DTMF_B=8", "-DTMF_RAGGED_PART=1"] + ILP), (tu, ["-DTMF_B=8", "-DTMF_RAGGED_PART=2"])]
+                    mine += [(tu, ["-DTMF_B=8", "-DTMF_RAGGED_PART=1"] + ILP), (tu, ["-DTMF_B=8", "-DTMF_RAGGED_PART=2"])]
                 elif (tu, b) == ("tmfwm_ragged_pre.hip", 8):  # two objects: the pre-pass, and the list pass under max-ILP
-                    out += [(tu, ["-DTMF_B=8", "-DTMF_RAGGED_PRE_PART=1"]), (tu, ["-DTMF_B=8", "-DTMF_RAGGED_PRE_PART=2"] + ILP)]
+                    mine += [(tu, ["-DTMF_B=8", "-DTMF_RAGGED_PRE_PART=1"]), (tu, ["-DTMF_B=8", "-DTMF_RAGGED_PRE_PART=2"] + ILP)]
                 elif (tu, b) == ("tmfwm_embed_key.hip", 8):  # under max-ILP, as embed_kernel<8>
-                    out.append((tu, ["-DTMF_B=8"] + ILP))
+                    mine.append((tu, ["-DTMF_B=8"] + ILP))
                 else:
-                    out.append((tu, ["-DTMF_B=%d" % b]))
+                    mine.append((tu, ["-DTMF_B=%d" % b]))
+            if tu in ALPHAS:  # each object once more as the per-frame form (the Makefile's ALPHA_OBJS), built as its sibling
+                mine += [(t, f + ["-DTMF_RAGGED_ALPHAS=1"]) for t, f in mine]
+            out += mine
         else:
             out.append((tu, ILP if tu == "tmfwm_embed8.hip" else []))
     return out + [("tmfwm_capi.cpp", ["-x", "hip"]), ("tmfwm_multi.cpp", ["-x", "hip"])]
